@@ -17,12 +17,15 @@ construction), credit_card-shaped synthetic data (30 features, 0.17% fraud, Baye
 
 value = post-SMOTE training rows fitted per second, whole job (sum over ranks / slowest rank's
 time).  Baseline = 3.50 M rows/s: sklearn lbfgs fit alone on the 10M-row post-SMOTE set
-(our step additionally includes the scaler and SMOTE work).  After timing, the
-test AUC (exact, K10), the SGD fit's convergence state and objective against the Newton optimum on
-the same training set, the other solver / row formats, and the LinearSHAP / KernelSHAP
-throughputs are reported as extra fields.
+(our step additionally includes the scaler and SMOTE work).  A plain run sets up,
+warms up, times the K steps and prints the result line.  With --full it then also reports, as
+extra fields, the test AUC (exact, K10), the SGD fit's convergence state and objective against the
+Newton optimum on the same training set, the other solver / row formats, and the LinearSHAP /
+KernelSHAP throughputs.  --dump-outputs DIR writes what the last timed fit returned (weights,
+scaler parameters, row counts) as DIR/<name>.npy; the inputs are seeded, so two builds can be
+compared array for array.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
        torchrun --nproc-per-node N bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -44,7 +47,7 @@ BASELINE_LINEAR_SHAP_PER_S = 316e6      # BASELINE.md §2, LinearSHAP values/s a
 BASELINE_CPU_KERNELSHAP_PER_S = 4671.3
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -58,10 +61,38 @@ def parse():
                          "semantics (every rank a slice of one draw sequence over all minority rows; "
                          "exact k-NN over all of them, so per-rank k-NN work grows with N); shard = "
                          "per-partition SMOTE (constant per-rank work). auto: the headline uses global "
-                         "and a DP run ALSO times the shard scope, reported as shard_scope")
-    ap.add_argument("--no-extras", action="store_true", help="skip the post-timing AUC/SHAP measurements")
+                         "and a DP run with --full ALSO times the shard scope, reported as shard_scope")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the extra measurements (test AUC, convergence "
+                         "against Newton, the other solvers / row formats, CV jobs, SHAP, predict, GBDT); "
+                         "a plain run times the headline fit only")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="deprecated: a run without --full is already headline only (still accepted "
+                         "for older command lines; overrides --full)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed fit returned as DIR/<name>.npy (float64)")
     ap.add_argument("--json-out", default=None)
-    return ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def _wants_extras(args, cpu_mode: bool) -> bool:
+    """The extra measurements run only on request (--full), never in the CPU contract mode."""
+    return bool(args.full) and not args.no_extras and not cpu_mode
+
+
+def _dump_outputs(res, path: str) -> None:
+    """The last timed fit's result, as a caller of DevicePipeline.fit receives it: the
+    standardized-space weights (w[30] = intercept), the scaler's parameters and the row counts.
+    About 1 KB in all; the inputs are seeded, so two builds compare array for array."""
+    os.makedirs(path, exist_ok=True)
+    mean, var, scale = res.scaler.numpy()
+    arrays = {
+        "weights": res.w, "coef": res.coef, "intercept": [res.intercept],
+        "scaler_mean": mean, "scaler_var": var, "scaler_scale": scale,
+        "row_counts": [res.n_rows, res.n_train_rows, res.n_minority, res.n_synthetic],
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(np.asarray(a, dtype=np.float64)))
 
 
 def _free_port() -> int:
@@ -121,7 +152,6 @@ def main():
     if _cpu_mode():
         dev = torch.device("cpu")
         comm = Communicator(backend="gloo") if world_env > 1 else None
-        args.no_extras = True
     else:
         if not torch.cuda.is_available():
             print("bench.py requires a ROCm GPU (FDX_BENCH_DEVICE=cpu for the CPU contract test)", file=sys.stderr)
@@ -146,12 +176,13 @@ def main():
     n_test = n_total // 5
     n_train = n_total - n_test
     X, y = separable(n_train, seed=1000 + rank, device=dev)
-    Xt, yt = separable(n_test, seed=5000 + rank, device=dev)
+    want_extras = _wants_extras(args, _cpu_mode())
+    if want_extras:  # the test split: only the extras evaluate on it
+        Xt, yt = separable(n_test, seed=5000 + rank, device=dev)
 
     scope = args.smote_scope if args.smote_scope != "auto" else "global"
     cfg = TrainConfig(solver=args.solver, storage=args.storage, seed=42, smote_scope=scope)
     pipe = DevicePipeline(cfg, comm)
-    rng = np.random.default_rng(7)
 
     def step():
         # random-init weights each fit (reference model family, no checkpoint)
@@ -197,8 +228,11 @@ def main():
     raw_global = comm.all_reduce_scalar(float(n_train)) if comm else float(n_train)
     value = rows_global / (ms_per_step / 1000.0)
 
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(res, args.dump_outputs)
+
     extras = {}
-    if not args.no_extras:
+    if want_extras:
         ev = evaluate(res, Xt, yt, comm)
         extras["auc"] = round(ev["auc"], 6)
         extras["confusion"] = {k: ev[k] for k in ("tn", "fp", "fn", "tp")}

@@ -7,8 +7,8 @@
 #   tests        pytest -m gpu (one process, per-test timeout)
 #   tests:<expr> pytest -m gpu -k <expr>
 #   smoke        __graft_entry__.smoke()
-#   bench        bench.py defaults (N=1)
-#   bench50      bench.py --steps 50
+#   bench        bench.py --full, default steps (N=1)
+#   bench50      bench.py --full --steps 50
 #   configs      tools/baseline_configs.py (every BASELINE config)
 #   ubench       tools/ubench.py per-kernel event timings
 #   schedlab     tools/sched_lab.py: Newton warm-up schedules on the virtual-SMOTE bench fit
@@ -19,7 +19,7 @@
 #   proffp8      the same with fp8 training rows
 #   profsgd      kernel trace + one-step timeline of the SGD fit
 #   marker       rocprofv3 --marker-trace --kernel-trace with the pipeline's roctx phase markers
-#   benchfp8     bench.py --storage fp8
+#   benchfp8     bench.py --full --storage fp8
 #   quick        bench.py --solver newton --no-extras, bf16 then fp8 (20 steps); quickfuse: fused Newton iterations (FDX_NEWTON_FUSE=1); proffuse: their trace
 #   quicksgd     the same with the SGD solver
 #   quicksgdnc   quicksgd bf16 with the cooperative persistent launch (FDX_SGD_COOP=1)
@@ -60,9 +60,9 @@ for st in "$@"; do
     tests) step tests 1000 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread ;;
     tests:*) step tests_k 900 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread -k "${st#tests:}" ;;
     smoke) step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) step bench 600 python bench.py ;;
-    bench50) step bench50 600 python bench.py --steps 50 --warmup 5 ;;
-    benchfp8) step benchfp8 600 python bench.py --storage fp8 ;;
+    bench) step bench 600 python bench.py --full ;;
+    bench50) step bench50 600 python bench.py --steps 50 --warmup 5 --full ;;
+    benchfp8) step benchfp8 600 python bench.py --storage fp8 --full ;;
     quicksgd) step quicksgd_bf16 300 python bench.py --steps 20 --warmup 3 --no-extras --solver sgd &&
            step quicksgd_fp8 300 python bench.py --steps 20 --warmup 3 --no-extras --solver sgd --storage fp8 ;;
     smoteov)  # the virtual-SMOTE bucket sort beside the scaler pass / beside the k-NN / in line (quick SGD benches)
@@ -221,10 +221,10 @@ for st in "$@"; do
     dp2)  # DP rehearsal on one GPU: 2 ranks over host-staged gloo (the RCCL path needs a GPU per rank)
       step dp2 300 env FDX_BENCH_ONE_GPU=1 FDX_BENCH_BACKEND=gloo python -m torch.distributed.run --nnodes=1 \
         --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 3 --warmup 1 \
-        --rows-per-gpu 2000000 ;;
+        --rows-per-gpu 2000000 --full ;;
     dp2self)  # bench.py --gpus 2 starts its own 2 ranks (self-launch path), one GPU, gloo
       step dp2self 300 env FDX_BENCH_ONE_GPU=1 FDX_BENCH_BACKEND=gloo python bench.py --gpus 2 --steps 3 --warmup 1 \
-        --rows-per-gpu 2000000 ;;
+        --rows-per-gpu 2000000 --full ;;
     dpscope)  # global vs shard SMOTE scope attribution (2 ranks, one GPU, gloo): per-fit times, phases, host profile
       step dpscope 400 env FDX_BENCH_ONE_GPU=1 FDX_BENCH_BACKEND=gloo python -m torch.distributed.run --nnodes=1 \
         --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29519 tools/dp_scope_probe.py --rows 2000000 ;;
