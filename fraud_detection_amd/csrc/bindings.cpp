@@ -445,15 +445,24 @@ PYBIND11_MODULE(_fdx_native, m) {
     fdx::launch_fp8_prescale(P<const float>(X), n, d, ns, stride, P<double>(partial), P<double>(sums), P<float>(mu),
                              P<float>(k), S(s));
   });
-  m.def("scaler_stats_cast_blocks", [](int fp8) { return fdx::scaler_stats_cast_blocks(fp8); }, py::arg("fp8") = 0);
+  m.def("scaler_stats_cast_blocks", [](int fp8, int minority) { return fdx::scaler_stats_cast_blocks(fp8, minority); },
+        py::arg("fp8") = 0, py::arg("minority") = 0);
   m.def("scaler_stats_cast", [](u X, int64_t n, int d, u pivot, u labels, float bias_value, u out, u partial,
-                                int nblocks, u s, u colscale, float out_scale, u idx) {
+                                int nblocks, u s, u colscale, float out_scale, u idx, u min_off, u tinfo, u tmask,
+                                u xraw, int64_t cap, int target) {
     fdx::launch_scaler_stats_cast(P<const float>(X), n, d, P<const float>(pivot), P<const uint8_t>(labels), bias_value,
                                   P<void>(out), P<double>(partial), nblocks, S(s), P<const float>(colscale), out_scale,
-                                  P<const int64_t>(idx));
+                                  P<const int64_t>(idx), P<const int64_t>(min_off), P<const uint32_t>(tinfo),
+                                  P<const void>(tmask), P<float>(xraw), cap, target);
   }, py::arg("X"), py::arg("n"), py::arg("d"), py::arg("pivot"), py::arg("labels"), py::arg("bias_value"),
      py::arg("out"), py::arg("partial"), py::arg("nblocks"), py::arg("s"), py::arg("colscale") = 0,
-     py::arg("out_scale") = 1.0f, py::arg("idx") = 0);
+     py::arg("out_scale") = 1.0f, py::arg("idx") = 0, py::arg("min_off") = 0, py::arg("tinfo") = 0,
+     py::arg("tmask") = 0, py::arg("xraw") = 0, py::arg("cap") = 0, py::arg("target") = 1);
+  m.def("compact_count_tiles_blocks", [](int64_t n) { return fdx::compact_count_tiles_blocks(n); });
+  m.def("compact_count_tiles", [](u labels, int64_t n, int target, u counts, u tinfo, u tmask, u s) {
+    fdx::launch_compact_count_tiles(P<const uint8_t>(labels), n, target, P<int64_t>(counts), P<uint32_t>(tinfo),
+                                    P<void>(tmask), S(s));
+  });
   m.def("scale_cast", [](u X, int64_t n, int ld, int d, u idx, u mean32, u inv32, u labels, float bias_value,
                          float out_scale, int out_kind, u out, u s) {
     fdx::launch_scale_cast(P<const float>(X), n, ld, d, P<const int64_t>(idx), P<const float>(mean32),
@@ -808,6 +817,20 @@ PYBIND11_MODULE(_fdx_native, m) {
   }, py::arg("X"), py::arg("m"), py::arg("m_pad"), py::arg("role"), py::arg("out"), py::arg("s"),
      py::arg("outq") = 0, py::arg("aff") = 0, py::arg("parents") = 0, py::arg("chl") = 0, py::arg("qhl") = 0,
      py::arg("tmax") = 0);
+  // nparts > 0: the scaler finalize is folded in (sums / n / pivot / colscale in, the six stats arrays out);
+  // nparts == 0: mean32 / inv32 / aff are read
+  m.def("knn_prep_raw", [](u Xraw, int m_, int m_pad, u out, u outq, u parents, u s, int d, int nparts, double n,
+                           u sums, u pivot, u colscale, u mean64, u var64, u scale64, u mean32, u inv32, u aff,
+                           u chl, u qhl, u tmax) {
+    fdx::KnnRawStats st{d, nparts, n, P<const double>(sums), P<const float>(pivot), P<const float>(colscale),
+                        P<double>(mean64), P<double>(var64), P<double>(scale64), P<float>(mean32), P<float>(inv32),
+                        P<double>(aff)};
+    fdx::launch_knn_prep_raw(P<const float>(Xraw), m_, m_pad, P<float>(out), P<float>(outq), P<uint16_t>(parents), st,
+                             S(s), P<void>(chl), P<void>(qhl), P<float>(tmax));
+  }, py::arg("Xraw"), py::arg("m"), py::arg("m_pad"), py::arg("out"), py::arg("outq"), py::arg("parents"),
+     py::arg("s"), py::arg("d"), py::arg("nparts"), py::arg("n"), py::arg("sums"), py::arg("pivot"),
+     py::arg("colscale"), py::arg("mean64"), py::arg("var64"), py::arg("scale64"), py::arg("mean32"),
+     py::arg("inv32"), py::arg("aff"), py::arg("chl") = 0, py::arg("qhl") = 0, py::arg("tmax") = 0);
   m.def("knn_splits", [](int mq_pad, int mc_pad) { return fdx::knn_splits(mq_pad, mc_pad); });
   m.def("knn_lds_splits", [](int mq_pad, int mc_pad) { return fdx::knn_lds_splits(mq_pad, mc_pad); });
   m.def("knn_topk_lds", [](u Q, int mq_pad, int mq, u C, int mc_pad, int mc, int64_t self_off, int k, u oidx,

@@ -19,6 +19,7 @@
 
 #include "common.h"
 #include "launchers.h"
+#include "scaler_finalize.h"
 
 namespace fdx {
 namespace {
@@ -61,12 +62,31 @@ __device__ __forceinline__ void topk_insert(float (&bs)[K], int (&bi)[K], float 
 // launch -- knn_split_kernel's role 2 (candidates, fragment order, per-tile norm bound) and role 1
 // (queries, row order) on the values this thread just wrote, bitwise the same -- so the self-search
 // of the bf16x3 engines needs no split launches.
+// RAW (knn_prep_raw_kernel, the fused minority chain): X holds RAW padded minority rows (the
+// scaler pass's xraw: features, zeros, bias, label) and every feature is standardized as it is
+// read, z = (x - mean32) * inv32 -- scale_cast_kernel's subtract-then-multiply, so everything
+// below sees the bits the gather + scale_cast launch used to write.  st: [4][32] floats in LDS,
+// mean32 | inv32 | (float)(1 / aff[32 + c]) | (float)aff[c] (the parents' map, as computed below).
 __device__ __forceinline__ void split_row(const float (&x)[32], uint32_t (&h)[16], uint32_t (&l)[16]);
-__global__ void knn_prep_kernel(const float* __restrict__ X, int m, int m_pad, int role,
-                                float* __restrict__ out, float* __restrict__ outq,
-                                const double* __restrict__ aff, uint16_t* __restrict__ P,
-                                uint4* __restrict__ chl = nullptr, uint4* __restrict__ qhl = nullptr,
-                                float* __restrict__ tmax = nullptr) {
+template <bool RAW>
+__device__ __forceinline__ float4 prep_load(const float4* __restrict__ p, int k, const float* st, int d) {
+#pragma clang fp contract(off)
+  float4 v = p[k];
+  if constexpr (RAW) {
+    const int c = 4 * k;
+    if (c < d) v.x = (v.x - st[c]) * st[32 + c];
+    if (c + 1 < d) v.y = (v.y - st[c + 1]) * st[32 + c + 1];
+    if (c + 2 < d) v.z = (v.z - st[c + 2]) * st[32 + c + 2];
+    if (c + 3 < d) v.w = (v.w - st[c + 3]) * st[32 + c + 3];
+  }
+  return v;
+}
+template <bool RAW>
+__device__ __forceinline__ void knn_prep_body(const float* __restrict__ X, int m, int m_pad, int role,
+                                              float* __restrict__ out, float* __restrict__ outq,
+                                              const double* __restrict__ aff, uint16_t* __restrict__ P,
+                                              uint4* __restrict__ chl, uint4* __restrict__ qhl,
+                                              float* __restrict__ tmax, const float* st, int d) {
 #pragma clang fp contract(off)  // the parents' mul-then-add must match smote_parents_kernel
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (chl != nullptr) {  // the fused split (blockDim 256, m_pad % 32 == 0: whole tiles per wave half)
@@ -77,7 +97,7 @@ __global__ void knn_prep_kernel(const float* __restrict__ X, int m, int m_pad, i
       float s = 0.0f;
 #pragma unroll
       for (int k = 0; k < kCols / 4; ++k) {
-        float4 v = p[k];
+        float4 v = prep_load<RAW>(p, k, st, d);
         if (k == kCols / 4 - 1) {
           s = fmaf(v.x, v.x, s); s = fmaf(v.y, v.y, s);
           v.z = 0.0f; v.w = 0.0f;
@@ -135,10 +155,18 @@ __global__ void knn_prep_kernel(const float* __restrict__ X, int m, int m_pad, i
   float s = 0.0f;
 #pragma unroll
   for (int k = 0; k < kCols / 4; ++k) {
-    float4 v = p[k];
+    float4 v = prep_load<RAW>(p, k, st, d);
     if (pp) {
       float4 u = v;
-      if (aff != nullptr) {
+      if constexpr (RAW) {
+        const int c = 4 * k;
+        u.x = u.x * st[64 + c] + st[96 + c];
+        u.y = u.y * st[64 + c + 1] + st[96 + c + 1];
+        if (c + 2 < kBiasCol) {
+          u.z = u.z * st[64 + c + 2] + st[96 + c + 2];
+          u.w = u.w * st[64 + c + 3] + st[96 + c + 3];
+        }
+      } else if (aff != nullptr) {
         const int c = 4 * k;
         u.x = u.x * (float)(1.0 / aff[32 + c]) + (float)aff[c];
         u.y = u.y * (float)(1.0 / aff[32 + c + 1]) + (float)aff[c + 1];
@@ -160,6 +188,50 @@ __global__ void knn_prep_kernel(const float* __restrict__ X, int m, int m_pad, i
   }
   out[(int64_t)r * kCols + 30] = role == 1 ? 1.0f : -0.5f * s;
   if (oq) outq[(int64_t)r * kCols + 30] = 1.0f;
+}
+
+
+__global__ void knn_prep_kernel(const float* __restrict__ X, int m, int m_pad, int role,
+                                float* __restrict__ out, float* __restrict__ outq,
+                                const double* __restrict__ aff, uint16_t* __restrict__ P,
+                                uint4* __restrict__ chl = nullptr, uint4* __restrict__ qhl = nullptr,
+                                float* __restrict__ tmax = nullptr) {
+  knn_prep_body<false>(X, m, m_pad, role, out, outq, aff, P, chl, qhl, tmax, nullptr, 0);
+}
+
+// The self-search prep (role 2) of the fused minority chain: raw minority rows in, and the scaler
+// finalize folded in.  st.nparts > 0: every block recomputes the statistics of its 32 columns
+// from the level-1 partials (scaler_finalize_col: scaler_finalize_kernel's own arithmetic) in its
+// prologue -- no finalize launch in front of the prep -- and block 0 writes the ScalerStats
+// outputs.  st.nparts == 0: mean32 / inv32 / aff are read from a finalize launch's outputs.
+__global__ __launch_bounds__(256) void knn_prep_raw_kernel(const float* __restrict__ X, int m, int m_pad,
+                                                           float* __restrict__ out, float* __restrict__ outq,
+                                                           uint16_t* __restrict__ P, uint4* __restrict__ chl,
+                                                           uint4* __restrict__ qhl, float* __restrict__ tmax,
+                                                           KnnRawStats st) {
+  __shared__ float sst[4 * 32];
+  if (threadIdx.x < 32) {
+    const int c = threadIdx.x;
+    float mu, inv;
+    double ac, ai;
+    if (st.nparts > 0) {
+      const ScalerCol o = scaler_finalize_col(st.sums, st.n, st.pivot, st.d, st.colscale, st.nparts, c);
+      mu = o.mean32; inv = o.inv32; ac = o.aff_c; ai = o.aff_inv;
+      if (blockIdx.x == 0) {
+        st.mean64[c] = o.mean; st.var64[c] = o.var; st.scale64[c] = o.scale;
+        st.mean32[c] = mu; st.inv32[c] = inv;
+        st.aff[c] = ac; st.aff[32 + c] = ai;
+      }
+    } else {
+      mu = st.mean32[c]; inv = st.inv32[c]; ac = st.aff[c]; ai = st.aff[32 + c];
+    }
+    sst[c] = mu;
+    sst[32 + c] = inv;
+    sst[64 + c] = (float)(1.0 / ai);
+    sst[96 + c] = (float)ac;
+  }
+  __syncthreads();
+  knn_prep_body<true>(X, m, m_pad, 2, out, outq, nullptr, P, chl, qhl, tmax, sst, st.d);
 }
 
 // Q: [mq_pad][32] query rows and C: [mc_pad][32] candidate rows, both from knn_prep_kernel.
@@ -1505,6 +1577,23 @@ void launch_knn_prep(const float* X, int m, int m_pad, int role, float* out, flo
   knn_prep_kernel<<<(m_pad + 255) / 256, 256, 0, stream>>>(X, m, m_pad, role, out, outq, aff, P,
                                                             static_cast<uint4*>(chl), static_cast<uint4*>(qhl), tmax);
   check_launch("knn_prep");
+}
+
+void launch_knn_prep_raw(const float* Xraw, int m, int m_pad, float* out, float* outq, uint16_t* P,
+                         const KnnRawStats& st, hipStream_t stream, void* chl, void* qhl, float* tmax) {
+  if (Xraw == nullptr || out == nullptr || outq == nullptr || m < 0 || m_pad < m)
+    throw std::invalid_argument("knn_prep_raw: rows and both operand outputs");
+  if ((chl != nullptr || qhl != nullptr || tmax != nullptr) &&
+      (chl == nullptr || qhl == nullptr || tmax == nullptr || m_pad % 32 != 0))
+    throw std::invalid_argument("knn_prep_raw: the fused split needs all three outputs and m_pad % 32 == 0");
+  if (st.d < 1 || st.d > kCols - 2 || st.nparts < 0 || st.nparts > 128 || st.mean32 == nullptr ||
+      st.inv32 == nullptr || st.aff == nullptr ||
+      (st.nparts > 0 && (st.sums == nullptr || st.pivot == nullptr || st.mean64 == nullptr || st.var64 == nullptr ||
+                         st.scale64 == nullptr)))
+    throw std::invalid_argument("knn_prep_raw: bad statistics block");
+  knn_prep_raw_kernel<<<(m_pad + 255) / 256, 256, 0, stream>>>(Xraw, m, m_pad, out, outq, P, static_cast<uint4*>(chl),
+                                                                static_cast<uint4*>(qhl), tmax, st);
+  check_launch("knn_prep_raw");
 }
 
 int knn_splits(int mq_pad, int mc_pad) {

@@ -50,13 +50,25 @@ void launch_fp8_hw_check(float* dec, const float* vals, int n, uint8_t* enc, hip
 int fp8_prescale_blocks();  // partial rows ([n][64] fp64) launch_fp8_prescale needs
 void launch_fp8_prescale(const float* X, int64_t n, int d, int64_t ns, int64_t stride, double* partial,
                          double* sums, float* mu, float* k, hipStream_t stream);
-int scaler_stats_cast_blocks(int fp8 = 0);  // resident blocks of the fused kernel (per row format)
+// resident blocks of the fused kernel (per row format; minority: the form that also writes xraw)
+int scaler_stats_cast_blocks(int fp8 = 0, int minority = 0);
 // fused K1+K2: shifted sums -> partial[nblocks][64], rows s = x - pivot in bf16, or (colscale set)
-// fp8 e4m3 of (x - pivot) * colscale * out_scale
+// fp8 e4m3 of (x - pivot) * colscale * out_scale.
+// xraw (optional, [cap][32] fp32): the raw rows with label == target, in row order, padded (cols
+// d..29 zero, col 30 bias_value, col 31 the label); min_off / tinfo / tmask from launch_compact_count_tiles
+// + launch_exclusive_scan_small; rows at positions >= cap are dropped
 void launch_scaler_stats_cast(const float* X, int64_t n, int d, const float* pivot, const uint8_t* labels,
                               float bias_value, void* out, double* partial, int nblocks, hipStream_t stream,
                               const float* colscale = nullptr, float out_scale = 1.0f,
-                              const int64_t* idx = nullptr);
+                              const int64_t* idx = nullptr, const int64_t* min_off = nullptr,
+                              const uint32_t* tinfo = nullptr, const void* tmask = nullptr, float* xraw = nullptr,
+                              int64_t cap = 0, int target = 1);
+// per-tile form of compact_count for the fused pass: counts[compact_count_tiles_blocks(n)] block
+// totals (to be scanned in place), tinfo[ceil(n / 128)] = in-block prefix | tile count << 16 and
+// tmask[ceil(n / 128)] (16 bytes each, 16-byte aligned) = the tile's label match bits
+int compact_count_tiles_blocks(int64_t n);
+void launch_compact_count_tiles(const uint8_t* labels, int64_t n, int target, int64_t* counts, uint32_t* tinfo,
+                                void* tmask, hipStream_t stream);
 void launch_scale_cast(const float* X, int64_t n, int ld, int d, const int64_t* idx,
                        const float* mean32, const float* inv32, const uint8_t* labels,
                        float bias_value, float out_scale, int out_kind, void* out,
@@ -292,6 +304,26 @@ int sgd_persist_blocks(int grid_blocks);
 void launch_knn_prep(const float* X, int m, int m_pad, int role, float* out, float* outq,
                      const double* aff, uint16_t* P, hipStream_t stream, void* chl = nullptr, void* qhl = nullptr,
                      float* tmax = nullptr);
+// Statistics for launch_knn_prep_raw.  nparts > 0 (finalize folded in): sums = [nparts][64]
+// level-1 scaler partials, n / pivot / colscale as for launch_scaler_finalize, and the six
+// ScalerStats arrays are OUTPUTS (written by block 0).  nparts == 0: mean32 / inv32 / aff are
+// inputs (a finalize launch's outputs), the rest unused.
+struct KnnRawStats {
+  int d, nparts;
+  double n;
+  const double* sums;
+  const float* pivot;
+  const float* colscale;
+  double *mean64, *var64, *scale64;
+  float *mean32, *inv32;
+  double* aff;
+};
+// role-2 prep (self-search) from RAW padded minority rows (launch_scaler_stats_cast's xraw):
+// standardizes with (x - mean32) * inv32 on the fly, then writes what launch_knn_prep writes
+// (P nullable; chl / qhl / tmax all or none)
+void launch_knn_prep_raw(const float* Xraw, int m, int m_pad, float* out, float* outq, uint16_t* P,
+                         const KnnRawStats& st, hipStream_t stream, void* chl = nullptr, void* qhl = nullptr,
+                         float* tmax = nullptr);
 int knn_splits(int mq_pad, int mc_pad);
 // bf16x3 MFMA filter + exact fp32 re-score (knn.hip): hl [m_pad][8] uint4 = hi | lo bf16 rows of
 // the prepped rows; tmax [mc_pad / 32] max candidate norm per tile (role 0 only)

@@ -15,6 +15,7 @@
 #include "common.h"
 #include "compact.h"
 #include "launchers.h"
+#include "scaler_finalize.h"
 
 namespace fdx {
 
@@ -128,6 +129,9 @@ __global__ __launch_bounds__(kThreads) void scaler_partial_kernel(const float* _
 // coalesced 16 B loads into LDS; thread (column c = tid & 31, row group tid >> 5) then walks
 // its column of the tile (consecutive lanes read consecutive floats: conflict-free).
 constexpr int kStatTileRows = 128;
+// tiles per block of compact_count_tiles_kernel (one thread per tile): a block's in-block
+// minority prefix is <= 255 * 128 < 2^16
+constexpr int kTilesPerBlock = kCompactThreads;
 
 __global__ __launch_bounds__(kThreads) void scaler_partial_tiled_kernel(const float* __restrict__ X,
                                                                         int64_t n, int d,
@@ -200,12 +204,23 @@ __device__ __forceinline__ int stats_fetch(const float* __restrict__ X, int64_t 
 // Scatter form (IDX: cross-validation, models/cv.py): row i is written to output row idx[i] -- the
 // fold-sorted training table is cast from the raw table read in order (64-byte rows land whole at
 // scattered positions; gathering the 120-byte raw rows instead ran at a third of the stream rate).
-template <bool NT, bool FP8, bool IDX = false>
-__global__ __launch_bounds__(kThreads, FP8 ? 6 : 8) void scaler_stats_cast_kernel(
+// Minority output (MIN: the single-process SMOTE fit): the raw fp32 rows whose label == target are
+// also written, in row order, to xraw [cap][32] (cols d..29 zero, col 30 = bias_value, col 31 =
+// label) straight from the LDS tile -- the k-NN prep standardizes them (knn.hip knn_prep_raw), so
+// no index list, no gather of 120-byte rows from the raw matrix and no fp32 copy of the
+// standardized rows.  min_off / tinfo / tmask: compact_count_tiles_kernel's scanned block offsets,
+// per-tile (prefix | count << 16) and per-tile label match mask; at a 0.17 % minority rate 4 tiles
+// in 5 hold none and cost one uniform branch, and the others read no label.  Rows at positions >= cap are dropped (the host sees the total and falls back).
+// (MIN fp8: bound to the 7 blocks per CU the plain fp8 form reaches at 72 VGPRs; left at 6 the
+// compiler took 76)
+template <bool NT, bool FP8, bool IDX = false, bool MIN = false>
+__global__ __launch_bounds__(kThreads, FP8 ? (MIN ? 7 : 6) : 8) void scaler_stats_cast_kernel(
     const float* __restrict__ X, int64_t n, int d, const float* __restrict__ pivot,
     const uint8_t* __restrict__ labels, float bias_value, void* __restrict__ outv,
     double* __restrict__ partial, const float* __restrict__ colscale, float out_scale,
-    const int64_t* __restrict__ idx) {
+    const int64_t* __restrict__ idx, const int64_t* __restrict__ min_off = nullptr,
+    const uint32_t* __restrict__ tinfo = nullptr, const uint4* __restrict__ tmask = nullptr,
+    float* __restrict__ xraw = nullptr, int64_t cap = 0, int target = 1) {
   __shared__ __attribute__((aligned(16))) float tile[kStatTileRows * 30];
   __shared__ double red[2][8][32];
   const int c = threadIdx.x & 31, rg = threadIdx.x >> 5;
@@ -226,7 +241,19 @@ __global__ __launch_bounds__(kThreads, FP8 ? 6 : 8) void scaler_stats_cast_kerne
   float tail = 0.0f;
   int64_t t = blockIdx.x;
   int nf = 0;
+  // MIN: this tile's (minority prefix | count << 16), 128-bit label match mask and count-block
+  // offset -- block-uniform scalar loads, fetched one tile ahead like the rows
+  uint32_t ti = 0;
+  uint4 tm = make_uint4(0u, 0u, 0u, 0u);
+  int64_t boff = 0;
   if (t < ntiles) nf = stats_fetch(X, t, d, total, b0, b1, b2, b3, tail);
+  if constexpr (MIN) {
+    if (t < ntiles) {
+      ti = tinfo[t];
+      tm = tmask[t];
+      boff = min_off[t / kTilesPerBlock];
+    }
+  }
   for (; t < ntiles; t += gridDim.x) {
     {
       const int nf4 = nf >> 2, i = threadIdx.x;
@@ -235,11 +262,48 @@ __global__ __launch_bounds__(kThreads, FP8 ? 6 : 8) void scaler_stats_cast_kerne
       if (i + kThreads < nf4) t4[i + kThreads] = b1;
       if (i + 2 * kThreads < nf4) t4[i + 2 * kThreads] = b2;
       if (i + 3 * kThreads < nf4) t4[i + 3 * kThreads] = b3;
-      const int ti = (nf4 << 2) + threadIdx.x;
-      if (ti < nf) tile[ti] = tail;
+      const int tl = (nf4 << 2) + threadIdx.x;
+      if (tl < nf) tile[tl] = tail;
     }
     __syncthreads();
     const int rows = nf / d;
+    // MIN: here, between the barrier and the next tile's prefetch, the 17 double-buffer registers are
+    // dead -- after the prefetch the section's few temporaries spilled (the bf16 form sits at its
+    // 64-VGPR bound)
+    if constexpr (MIN) {
+      if ((ti >> 16) != 0) {  // this tile holds minority rows: no memory read on this path but the LDS tile
+        // Everything per-lane is derived here from a laundered thread id, so nothing of this rare
+        // section is hoisted out of the tile loop into registers that stay live across the cast
+        // (which spilled); the output row's base is uniform.
+        int tid = threadIdx.x;
+        asm volatile("" : "+v"(tid));
+        const int mc = tid & 31, mrg = tid >> 5;
+        const int64_t base = boff + (int64_t)(ti & 0xffffu);
+        // fill of the columns past d: zeros, the bias, the label
+        const float pad = mc == kBiasCol ? bias_value : (mc == kLabelCol ? (float)target : 0.0f);
+        const uint32_t mw[4] = {tm.x, tm.y, tm.z, tm.w};
+        int j = 0;  // in-tile rank: half-wave (j & 7) writes the row's 32 columns (128 B)
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+          uint32_t m = mw[w];
+          while (m) {
+            const int r = 32 * w + __builtin_ctz(m);
+            m &= m - 1;
+            if (base + j < cap) {  // uniform
+              float* __restrict__ orow = xraw + (base + j) * kCols;
+              if ((j & 7) == mrg) orow[mc] = mc < d ? tile[r * d + mc] : pad;
+            }
+            ++j;
+          }
+        }
+      }
+      // the next tile's words, in flight across the reduce and the cast
+      if (t + gridDim.x < ntiles) {
+        ti = tinfo[t + gridDim.x];
+        tm = tmask[t + gridDim.x];
+        boff = min_off[(t + gridDim.x) / kTilesPerBlock];
+      }
+    }
     if (t + gridDim.x < ntiles) nf = stats_fetch(X, t + gridDim.x, d, total, b0, b1, b2, b3, tail);
     if (c < d) {
       for (int r = rg; r < rows; r += 8) {
@@ -330,44 +394,15 @@ __global__ void scaler_finalize_kernel(const double* __restrict__ sums, double n
                                        const float* __restrict__ colscale, int nparts) {
   const int c = threadIdx.x;
   if (c >= kCols) return;
-  // nparts > 1: `sums` holds the first-level reduce's [nparts][64] rows, summed here in order
-  // (the order of the second-level reduce launch this replaces: bit-identical sums)
-  double s1 = 0.0, s2 = 0.0, sn = 0.0;
-  for (int p = 0; p < nparts; ++p) {
-    s1 += sums[64 * p + c];
-    s2 += sums[64 * p + 32 + c];
-    sn += sums[64 * p + kCols - 1];
-  }
-  // n < 0: the (all-reduced) row count rides in the unused slot sums[31] (one collective for the
-  // sums and the count, and no host round trip for n)
-  if (n < 0.0) n = sn;
-  if (c < d) {
-    const double m = s1 / n;
-    const double mean = (double)pivot[c] + m;
-    double var = s2 / n - m * m;
-    if (var < 0.0) var = 0.0;
-    const double eps = 2.220446049250313e-16;
-    const double ub = n * eps * var + (n * mean * eps) * (n * mean * eps);
-    const double scale = (var <= ub) ? 1.0 : sqrt(var);
-    mean64[c] = mean;
-    var64[c] = var;
-    scale64[c] = scale;
-    mean32[c] = (float)mean;
-    inv32[c] = (float)(1.0 / scale);
-    if (aff) {
-      // mean - pivot, without the cancellation of (pivot + m) - pivot; fp8 rows store v = s * k
-      // (colscale), so z = (s - m) / scale = (v - k m) * (1 / (scale k))
-      const double k = colscale ? (double)colscale[c] : 1.0;
-      aff[c] = m * k;
-      aff[32 + c] = 1.0 / scale / k;
-    }
-  } else {
-    mean64[c] = 0.0; var64[c] = 0.0; scale64[c] = 1.0;
-    mean32[c] = 0.0f; inv32[c] = 0.0f;
-    if (aff) {
-      aff[c] = 0.0;
-      aff[32 + c] = 1.0;
-    }
+  const ScalerCol o = scaler_finalize_col(sums, n, pivot, d, colscale, nparts, c);
+  mean64[c] = o.mean;
+  var64[c] = o.var;
+  scale64[c] = o.scale;
+  mean32[c] = o.mean32;
+  inv32[c] = o.inv32;
+  if (aff) {
+    aff[c] = o.aff_c;
+    aff[32 + c] = o.aff_inv;
   }
 }
 
@@ -617,6 +652,51 @@ __global__ __launch_bounds__(kCompactThreads) void compact_count16_kernel(
   }
 }
 
+// Count variant for the fused pass's minority-row output: one thread per 128-row tile of the pass
+// (8 label groups, 128 contiguous bytes), kTilesPerBlock tiles per block.  Besides the block's
+// count (scanned by exclusive_scan_small_kernel like compact_count16's) it writes per tile
+//   tinfo[t] = (minority rows of the block's earlier tiles) | (minority rows of tile t) << 16,
+//   tmask[t] = bit r set iff row r of the tile matches (128 bits),
+// so the pass finds the stable output position of a tile's first minority row as
+// offsets[t / kTilesPerBlock] + (tinfo[t] & 0xffff), skips a tile without one on its count and
+// reads no label itself (a label load there sat in front of the next tile's prefetch: +7 us per pass).
+static_assert(kStatTileRows == 128 && (kTilesPerBlock - 1) * kStatTileRows < (1 << 16), "tinfo packing");
+
+__global__ __launch_bounds__(kCompactThreads) void compact_count_tiles_kernel(
+    const uint8_t* __restrict__ labels, int64_t n, int target, int64_t* __restrict__ counts,
+    uint32_t* __restrict__ tinfo, uint4* __restrict__ tmask) {
+  const int64_t ngroups = (n + 15) / 16, ntiles = (n + kStatTileRows - 1) / kStatTileRows;
+  const int64_t t = (int64_t)blockIdx.x * kTilesPerBlock + threadIdx.x;
+  const uint32_t pat = 0x01010101u * (uint32_t)(target & 0xff);
+  uint32_t m[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) m[i] = 8 * t + i < ngroups ? group_mask(labels, n, 8 * t + i, target, pat) : 0u;
+  int c = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) c += __popc(m[i]);
+  const int lane = lane_id(), w = wave_id();
+  int inc = c;  // inclusive scan within the wave
+#pragma unroll
+  for (int o = 1; o < kWave; o <<= 1) {
+    const int u = __shfl_up(inc, o, kWave);
+    if (lane >= o) inc += u;
+  }
+  __shared__ int wave_tot[kCompactThreads / kWave];
+  if (lane == kWave - 1) wave_tot[w] = inc;
+  __syncthreads();
+  int before = inc - c, total = 0;
+#pragma unroll
+  for (int i = 0; i < kCompactThreads / kWave; ++i) {
+    if (i < w) before += wave_tot[i];
+    total += wave_tot[i];
+  }
+  if (t < ntiles) {
+    tinfo[t] = (uint32_t)before | ((uint32_t)c << 16);
+    tmask[t] = make_uint4(m[0] | (m[1] << 16), m[2] | (m[3] << 16), m[4] | (m[5] << 16), m[6] | (m[7] << 16));
+  }
+  if (threadIdx.x == 0) counts[blockIdx.x] = total;
+}
+
 __global__ __launch_bounds__(kCompactThreads) void compact_write16_kernel(
     const uint8_t* __restrict__ labels, int64_t n, int target, const int64_t* __restrict__ offsets,
     int64_t* __restrict__ out_idx) {
@@ -816,17 +896,37 @@ void launch_fp8_prescale(const float* X, int64_t n, int d, int64_t ns, int64_t s
 
 // Each format's own occupancy: the fp8 instantiation holds more VGPRs (74 vs 68: 6 vs 7 blocks
 // per CU), and a grid sized for bf16 ran 256 fp8 blocks in a second round (+25 us per pass).
-int scaler_stats_cast_blocks(int fp8) {
+int scaler_stats_cast_blocks(int fp8, int minority) {
   static const int cap16 = resident_cap(scaler_stats_cast_kernel<false, false>, kThreads);
   static const int cap8 = resident_cap(scaler_stats_cast_kernel<false, true>, kThreads);
+  static const int cap16m = resident_cap(scaler_stats_cast_kernel<false, false, false, true>, kThreads);
+  static const int cap8m = resident_cap(scaler_stats_cast_kernel<false, true, false, true>, kThreads);
+  if (minority) return fp8 ? cap8m : cap16m;
   return fp8 ? cap8 : cap16;
 }
 
 void launch_scaler_stats_cast(const float* X, int64_t n, int d, const float* pivot, const uint8_t* labels,
                               float bias_value, void* out, double* partial, int nblocks, hipStream_t stream,
-                              const float* colscale, float out_scale, const int64_t* idx) {
+                              const float* colscale, float out_scale, const int64_t* idx,
+                              const int64_t* min_off, const uint32_t* tinfo, const void* tmask, float* xraw,
+                              int64_t cap, int target) {
   if (d > 30 || (reinterpret_cast<uintptr_t>(X) % 16) != 0 || (reinterpret_cast<uintptr_t>(out) % 16) != 0)
     throw std::invalid_argument("scaler_stats_cast: contiguous 16-byte aligned rows, d <= 30");
+  if (xraw != nullptr) {  // minority-row output (see the kernel)
+    if (idx != nullptr || labels == nullptr || min_off == nullptr || tinfo == nullptr || tmask == nullptr || cap < 0 ||
+        (reinterpret_cast<uintptr_t>(tmask) % 16) != 0)
+      throw std::invalid_argument("scaler_stats_cast: minority output needs labels, offsets and tile info, no scatter");
+    if (colscale != nullptr)
+      scaler_stats_cast_kernel<false, true, false, true><<<nblocks, kThreads, 0, stream>>>(
+          X, n, d, pivot, labels, bias_value, out, partial, colscale, out_scale, nullptr, min_off, tinfo,
+          static_cast<const uint4*>(tmask), xraw, cap, target);
+    else
+      scaler_stats_cast_kernel<false, false, false, true><<<nblocks, kThreads, 0, stream>>>(
+          X, n, d, pivot, labels, bias_value, out, partial, colscale, out_scale, nullptr, min_off, tinfo,
+          static_cast<const uint4*>(tmask), xraw, cap, target);
+    check_launch("scaler_stats_cast");
+    return;
+  }
   // every block must be resident at once (a second round of blocks would double the span);
   // nblocks is fixed by the caller (partial buffer), the grid-stride loop covers the rest
 #define FDX_SSC(NT, F8, I)                                                                                 \
@@ -894,6 +994,21 @@ void launch_compact_count(const uint8_t* labels, int64_t n, int target, int64_t*
   else
     compact_count_kernel<<<nblocks, kCompactThreads, 0, stream>>>(labels, n, target, counts);
   check_launch("compact_count");
+}
+int compact_count_tiles_blocks(int64_t n) {
+  const int64_t ntiles = (n + kStatTileRows - 1) / kStatTileRows;
+  const int64_t b = (ntiles + kTilesPerBlock - 1) / kTilesPerBlock;
+  return (int)(b < 1 ? 1 : b);
+}
+void launch_compact_count_tiles(const uint8_t* labels, int64_t n, int target, int64_t* counts, uint32_t* tinfo,
+                                void* tmask, hipStream_t stream) {
+  // group_mask's 16-byte loads need the alignment; counts: compact_count_tiles_blocks(n) entries
+  // (<= 4096 for the small scan), tinfo: one word per 128-row tile
+  if (!compact_vec(labels) || (reinterpret_cast<uintptr_t>(tmask) % 16) != 0 || (n + kStatTileRows - 1) / kStatTileRows > (int64_t)4096 * kTilesPerBlock)
+    throw std::invalid_argument("compact_count_tiles: 16-byte aligned labels, at most 4096 * 256 tiles");
+  compact_count_tiles_kernel<<<compact_count_tiles_blocks(n), kCompactThreads, 0, stream>>>(labels, n, target, counts,
+                                                                                              tinfo, static_cast<uint4*>(tmask));
+  check_launch("compact_count_tiles");
 }
 void launch_exclusive_scan_small(int64_t* a, int n, int64_t* total, hipStream_t stream, int64_t* host_total) {
   exclusive_scan_small_kernel<<<1, 1024, 0, stream>>>(a, n, total, host_total);

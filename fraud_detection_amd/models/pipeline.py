@@ -49,6 +49,14 @@ class TrainConfig:
     # map of its sums)
     fold_scaler: bool = True
     fp8_scale: float = DEFAULT_FP8_SCALE
+    # With fold_scaler, one process, SMOTE on: the fused scaler pass also writes the raw minority
+    # rows it already holds in LDS, and ONE k-NN prep launch finalizes the statistics, standardizes
+    # those rows and writes the k-NN operands and SMOTE parents -- no index list, no gather of the
+    # raw rows, no fp32 copy of the standardized minority rows, no finalize launch.  Bitwise the
+    # same fit.  Off (or FDX_FUSE_MINORITY=0): the index-list chain (finalize -> compact_write ->
+    # gather scale_cast -> prep), which also serves CPU tensors, host streaming, data parallelism
+    # and a minority share above ops/scaler.minority_capacity (n / 64).
+    fuse_minority: bool = True
     # minibatch SGD (config 3, ops/logreg.sgd_fit): `sgd_batches` disjoint strided minibatches per
     # epoch, curvature-normalised momentum steps (per-epoch step scalars), Polyak averaging over the
     # last epoch, convergence state on the epoch gradient
@@ -354,6 +362,25 @@ class DevicePipeline:
             if os.environ.get("FDX_SMOTE_OVERLAP", "knn") == "scaler":
                 self._fit_start = torch.cuda.Event()
                 self._fit_start.record()
+            # fused minority chain: the count in front of the pass is per 128-row tile, the pass
+            # emits the raw minority rows and leaves its finalize to the k-NN prep (_finish)
+            mino = None
+            if (cfg.fuse_minority and cfg.smote and comm is None and n > 0 and scaler_ops.minority_fusable(y)
+                    and os.environ.get("FDX_FUSE_MINORITY", "1") != "0"):
+                mino = scaler_ops.minority_rows_async(y, 1)
+                stats = scaler_ops.scaler_fit_cast(X, y, rows_cap[:n], fp8_scale=cfg.fp8_scale, minority=mino,
+                                                   defer_finalize=True)
+                tm.mark("scaler_fit")
+                n_min = mino.count()
+                raw = mino.rows()  # None: more minority rows than the buffer holds -> index-list chain
+                _maybe_fault(rank)
+
+                def xmin_by_index():
+                    stats.finalize()
+                    return scaler_ops.scale_cast(X, stats, labels=y, out_dtype="f32", idx=mino.pending.result())
+
+                return self._finish(stats, rows_cap, n, d, n_min, fused, tm, comm, rank, dev, xmin_by_index,
+                                    host_ordered=True, raw=raw)
             pending = scaler_ops.compact_indices_async(y, 1)
             stats = scaler_ops.scaler_fit_cast(X, y, rows_cap[:n], comm=comm, fp8_scale=cfg.fp8_scale)
             tm.mark("scaler_fit")
@@ -373,11 +400,13 @@ class DevicePipeline:
                             host_ordered=True)
 
     def _finish(self, stats, rows_cap, n, d, n_min, fused, tm, comm, rank, dev, get_xmin,
-                host_ordered: bool = False) -> PipelineResult:
+                host_ordered: bool = False, raw: torch.Tensor | None = None) -> PipelineResult:
         """SMOTE (+ DP exchange) and the solver on the device-resident training rows
         rows_cap[:n] (shared by the resident and the host-streaming preparation).  host_ordered:
         the host has waited for a compute-stream result enqueued behind every earlier kernel (the
-        minority count), so everything enqueued before this fit has finished."""
+        minority count), so everything enqueued before this fit has finished.  raw (one process,
+        fused minority chain): the RAW minority rows [n_min, 32] from the scaler pass, with
+        ``stats`` still owing its finalize -- the k-NN prep standardizes them and finalizes."""
         cfg = self.cfg
 
         def quota(n_r, nmin_r):
@@ -403,6 +432,13 @@ class DevicePipeline:
             tot = float(sum(r[1] + q for r, q in zip(ranks, new_per_rank)))
             pos = float(sum(r[0] + q for r, q in zip(ranks, new_per_rank)))
             class_w = (tot / (2.0 * max(tot - pos, 1.0)), tot / (2.0 * max(pos, 1.0)))
+        # the fused prep runs only where the k-NN does (one process: a quota and >= 2 minority rows);
+        # otherwise, and on the index-list chain, the finalize launch owed by the scaler pass goes here
+        if raw is not None and not (comm is None and n_new > 0 and n_min >= 2
+                                    and knn_ops.knn_engine(n_min, n_min) != "fp32lds"):  # (pads queries apart)
+            raw = None
+        if raw is None:
+            stats.finalize()
         virt = None
         # Both row formats, both solvers: the SMOTE samples are generated inside every pass instead of
         # being written once and streamed by every pass.  (fp8 Newton took stored rows until its pass
@@ -414,7 +450,7 @@ class DevicePipeline:
         # quota; shard scope has no collective in this block, so only a rank with its own quota enters
         if (sum(new_per_rank) > 0) if glob else (n_new > 0):
             # ---- minority rows in fp32, gathered across ranks (C3) -----------------------
-            xmin = get_xmin()
+            xmin = raw if raw is not None else get_xmin()
             if glob:
                 xall, counts = comm.all_gather_rows(xmin, counts=[r[0] for r in ranks])
                 q_off = int(sum(counts[:rank]))
@@ -479,9 +515,12 @@ class DevicePipeline:
             parents = None
             if n_new > 0 and n_min > 0:
                 parents = torch.empty((xall.shape[0], NCOLS), dtype=torch.bfloat16, device=dev)
-            nbr = knn_ops.knn_topk(xmin, xall, k=k, self_offset=q_off, parents=parents,
-                                   parents_affine=stats.aff if (fused and parents is not None) else None) \
-                if n_min > 0 else torch.empty((0, k), dtype=torch.int32, device=dev)
+            if raw is not None:  # raw rows in: the prep finalizes the scaler and standardizes them
+                nbr = knn_ops.knn_topk(raw, raw, k=k, self_offset=0, parents=parents, raw_stats=stats)
+            else:
+                nbr = knn_ops.knn_topk(xmin, xall, k=k, self_offset=q_off, parents=parents,
+                                       parents_affine=stats.aff if (fused and parents is not None) else None) \
+                    if n_min > 0 else torch.empty((0, k), dtype=torch.int32, device=dev)
             if glob:  # every rank needs every minority row's neighbour list (int32, k per row)
                 nbr, _ = comm.all_gather_rows(nbr, counts=[r[0] for r in ranks])
                 q_off = 0
@@ -494,7 +533,14 @@ class DevicePipeline:
                                                seed=cfg.seed, counter_base=0 if glob else rank)
                     if pre_w is not None:  # the side stream's buckets: the fit's passes wait for them
                         main = torch.cuda.current_stream(dev)
-                        if not _settled_on_host(bucket_done, main):
+                        # Fused minority chain: the compute stream's chain behind the scaler pass is
+                        # ~30 us shorter and the sort's last kernel now runs beside the k-NN collect
+                        # (about twice as long), so a host that polls for the sort enqueues the
+                        # solver after the k-NN has ended (up to 100 us of idle stream in the trace,
+                        # profiles/pr2_minority_fused).  One look, then the stream waits (a ~6 us
+                        # barrier packet) and the host stays ahead: 0.921 vs 0.963 ms per step.
+                        budget = 0.0 if (raw is not None and "FDX_SORT_POLL_US" not in os.environ) else None
+                        if not _settled_on_host(bucket_done, main, budget):
                             main.wait_event(bucket_done)
                         virt.adopt(pre_w)
                     else:  # the once-per-fit bucket sort of the samples' lambdas, timed as the SMOTE phase

@@ -72,7 +72,8 @@ def _check_parents(parents: torch.Tensor | None, C: torch.Tensor, affine: torch.
 
 def knn_topk(Q: torch.Tensor, C: torch.Tensor, k: int = 5, self_offset: int = -1, want_dist: bool = False,
              nsplit: int | None = None, engine: str | None = None, parents: torch.Tensor | None = None,
-             parents_affine: torch.Tensor | None = None, _diag: dict | None = None):
+             parents_affine: torch.Tensor | None = None, _diag: dict | None = None, raw_stats=None,
+             _operands: dict | None = None):
     """k nearest candidates (squared L2 over the 30 feature columns) of each query row.
 
     Q [mq, 32] / C [mc, 32] fp32 padded rows (columns 30/31, intercept and label, are ignored).  If ``self_offset >= 0``, query row q is candidate
@@ -85,6 +86,12 @@ def knn_topk(Q: torch.Tensor, C: torch.Tensor, k: int = 5, self_offset: int = -1
     Both return the exact fp32 ranking.
     ``parents`` (bf16 [mc, 32], optional): also filled with ``smote_parents(C, parents_affine)``
     by the operand-prep launch that already reads C (one launch fewer on the SMOTE path).
+    ``raw_stats`` (``ScalerStats``; device self-search only, ``Q is C``): the rows are RAW padded
+    minority rows (the fused scaler pass's ``MinorityRows.xraw[:count]``) and the prep launch
+    standardizes them itself, z = (x - mean32) * inv32, bit for bit what ``scale_cast(...,
+    out_dtype="f32", idx=...)`` wrote; ``parents`` are mapped through ``raw_stats.aff``
+    (``parents_affine`` must be None).  Stats whose finalize is still owed
+    (``scaler_fit_cast(defer_finalize=True)``) are finalized inside the same launch.
     """
     for t, nm in ((Q, "Q"), (C, "C")):
         if t.dim() != 2 or t.shape[1] != NCOLS or t.dtype != torch.float32:
@@ -97,6 +104,11 @@ def knn_topk(Q: torch.Tensor, C: torch.Tensor, k: int = 5, self_offset: int = -1
         raise ValueError(f"need at least k={k} candidates besides self, have {n_valid}")
     if self_offset >= 0 and self_offset + mq > mc:
         raise ValueError("self_offset + mq exceeds the candidate set")
+    if raw_stats is not None:
+        if not Q.is_cuda or Q.data_ptr() != C.data_ptr() or mq != mc or not Q.is_contiguous() or want_dist \
+                or parents_affine is not None or raw_stats.aff is None or self_offset != 0:
+            raise ValueError("raw_stats: a device self-search (Q is C, self_offset 0) over contiguous raw rows, "
+                             "stats with aff, no parents_affine, no distances")
     if not Q.is_cuda:
         if _check_parents(parents, C, parents_affine):
             parents.copy_(smote_parents(C, parents_affine))
@@ -124,12 +136,27 @@ def knn_topk(Q: torch.Tensor, C: torch.Tensor, k: int = 5, self_offset: int = -1
         # SMOTE self-search: one launch reads the rows once and writes both operands (+ parents, and
         # for the bf16x3 engines that stream candidate tiles, their hi/lo split)
         fuse = eng in ("bf16x3r", "b3top")
-        m.knn_prep(ptr(Cc), mc, mc_pad, 2, ptr(Cp), s, ptr(Qp), ptr(parents_affine), pp,
-                   ptr(Chl) if fuse else 0, ptr(Qhl) if fuse else 0, ptr(tmax) if fuse else 0)
+        hl = (ptr(Chl), ptr(Qhl), ptr(tmax)) if fuse else (0, 0, 0)
+        if raw_stats is not None:
+            st = raw_stats
+            f = st.take_pending()  # the finalize still owed: folded into this launch
+            if f is None:
+                f = {"sums": None, "n": 0.0, "pivot": None, "colscale": None, "nparts": 0}
+            m.knn_prep_raw(ptr(Cc), mc, mc_pad, ptr(Cp), ptr(Qp), pp, s, st.d, f["nparts"], f["n"], ptr(f["sums"]),
+                           ptr(f["pivot"]), ptr(f["colscale"]), ptr(st.mean64), ptr(st.var64), ptr(st.scale64),
+                           ptr(st.mean32), ptr(st.inv32), ptr(st.aff), *hl)
+        else:
+            m.knn_prep(ptr(Cc), mc, mc_pad, 2, ptr(Cp), s, ptr(Qp), ptr(parents_affine), pp, *hl)
         split_done = fuse
     else:
+        if raw_stats is not None:
+            raise ValueError("raw_stats: the fp32lds engine pads its queries apart from the candidates")
         m.knn_prep(ptr(Cc), mc, mc_pad, 0, ptr(Cp), s, 0, ptr(parents_affine), pp)
         m.knn_prep(ptr(Qc), mq, mq_pad, 1, ptr(Qp), s)
+    if _operands is not None:  # the prep launch's outputs (tests)
+        _operands.update(Cp=Cp, Qp=Qp)
+        if eng in ("bf16x3r", "b3top"):
+            _operands.update(Chl=Chl, Qhl=Qhl, tmax=tmax)
     idx = torch.empty((mq, k), device=Q.device, dtype=torch.int32)
     score = torch.empty((mq, k), device=Q.device, dtype=torch.float32) if want_dist else None
     if nsplit is not None:

@@ -30,6 +30,23 @@ class ScalerStats:
     # set by scaler_fit_cast: [64] float64 (c | 1/sigma) mapping pivot-shifted rows s = x - pivot
     # to standardized ones, z = (s - c) / sigma (identity beyond d)
     aff: torch.Tensor | None = None
+    # scaler_fit_cast(defer_finalize=True): the finalize kernel's arguments while the tensors above
+    # are still unwritten.  Either ``finalize()`` launches it, or the fused k-NN prep takes the
+    # arguments (``take_pending``), recomputes the statistics in its prologue and writes the tensors.
+    pending: dict | None = None
+
+    def finalize(self) -> "ScalerStats":
+        """Launch the deferred finalize kernel, if one is still owed (no-op otherwise)."""
+        p, self.pending = self.pending, None
+        if p is not None:
+            native().scaler_finalize(ptr(p["sums"]), p["n"], ptr(p["pivot"]), self.d, ptr(self.mean64), ptr(self.var64),
+                                     ptr(self.scale64), ptr(self.mean32), ptr(self.inv32), ptr(self.aff), p["stream"],
+                                     ptr(p["colscale"]), p["nparts"])
+        return self
+
+    def take_pending(self) -> dict | None:
+        p, self.pending = self.pending, None
+        return p
 
     @property
     def n(self) -> float:
@@ -38,6 +55,7 @@ class ScalerStats:
         return float(self.n_src)
 
     def to(self, device) -> "ScalerStats":
+        self.finalize()
         return ScalerStats(self.n_src, self.d, *(t.to(device) for t in
                                              (self.mean64, self.var64, self.scale64, self.mean32, self.inv32)),
                            aff=None if self.aff is None else self.aff.to(device))
@@ -53,6 +71,7 @@ class ScalerStats:
         return torch.addcmul(a[:32].float(), rows_f32, (1.0 / a[32:]).float())
 
     def numpy(self):
+        self.finalize()
         d = self.d
         return (self.mean64[:d].cpu().numpy(), self.var64[:d].cpu().numpy(), self.scale64[:d].cpu().numpy())
 
@@ -102,10 +121,12 @@ def _aff_cpu(sums: np.ndarray, n: float, scale: np.ndarray, d: int) -> torch.Ten
 
 
 def scaler_finalize(sums: torch.Tensor, n_total, pivot: torch.Tensor, d: int, want_aff: bool = False,
-                    colscale: torch.Tensor | None = None, nparts: int = 1) -> ScalerStats:
+                    colscale: torch.Tensor | None = None, nparts: int = 1, defer: bool = False) -> ScalerStats:
     """``n_total`` None: the count is in sums[31] (device) -- see scaler_fit.  ``colscale`` (fp8
     rows, [d] float32): the stored values are v = s * colscale, folded into ``aff``.  ``nparts``
-    (device): ``sums`` is [nparts][64] first-level reduce rows, summed in order by the kernel."""
+    (device): ``sums`` is [nparts][64] first-level reduce rows, summed in order by the kernel.
+    ``defer`` (device, with ``want_aff``): allocate the outputs but leave the launch to
+    ``ScalerStats.finalize()`` or to the fused k-NN prep (``ScalerStats.pending``)."""
     dev = sums.device
     if n_total is None and not sums.is_cuda:
         n_total = float(sums[31])
@@ -118,7 +139,6 @@ def scaler_finalize(sums: torch.Tensor, n_total, pivot: torch.Tensor, d: int, wa
             aff = torch.cat([aff[:32] * k, aff[32:] / k])
         return ScalerStats(float(n_total), d, torch.from_numpy(mean), torch.from_numpy(var),
                            torch.from_numpy(scale), torch.from_numpy(m32), torch.from_numpy(i32), aff=aff)
-    m = native()
     piv = _pivot_dev(pivot, d, dev)
     mean64 = torch.empty(32, device=dev, dtype=torch.float64)
     var64 = torch.empty_like(mean64)
@@ -126,11 +146,12 @@ def scaler_finalize(sums: torch.Tensor, n_total, pivot: torch.Tensor, d: int, wa
     mean32 = torch.empty(32, device=dev, dtype=torch.float32)
     inv32 = torch.empty_like(mean32)
     aff = torch.empty(64, device=dev, dtype=torch.float64) if want_aff else None
-    m.scaler_finalize(ptr(sums), -1.0 if n_total is None else float(n_total), ptr(piv), d, ptr(mean64), ptr(var64),
-                      ptr(scale64), ptr(mean32), ptr(inv32), ptr(aff), stream_of(sums),
-                      ptr(colscale if (want_aff and colscale is not None) else None), int(nparts))
     n_src = sums[31:32] if n_total is None else float(n_total)
-    return ScalerStats(n_src, d, mean64, var64, scale64, mean32, inv32, aff=aff)
+    st = ScalerStats(n_src, d, mean64, var64, scale64, mean32, inv32, aff=aff)
+    st.pending = {"sums": sums, "n": -1.0 if n_total is None else float(n_total), "pivot": piv,
+                  "colscale": colscale if (want_aff and colscale is not None) else None, "nparts": int(nparts),
+                  "stream": stream_of(sums)}
+    return st if defer else st.finalize()
 
 
 def scaler_fit(X: torch.Tensor, comm=None, pivot: torch.Tensor | None = None) -> ScalerStats:
@@ -156,13 +177,13 @@ def scaler_fit(X: torch.Tensor, comm=None, pivot: torch.Tensor | None = None) ->
 _GRID_CACHE: dict = {}
 
 
-def _stats_cast_grid(m, dev, fp8: bool = False) -> int:
+def _stats_cast_grid(m, dev, fp8: bool = False, minority: bool = False) -> int:
     """Every block of the fused pass resident at once (occupancy-derived, per row format).
     Leaving block slots free for the side-stream count kernels was measured no faster
     (profiles/r2_s6, reserveab)."""
-    key = (dev.index, bool(fp8))
+    key = (dev.index, bool(fp8), bool(minority))
     if key not in _GRID_CACHE:
-        _GRID_CACHE[key] = int(m.scaler_stats_cast_blocks(int(bool(fp8))))
+        _GRID_CACHE[key] = int(m.scaler_stats_cast_blocks(int(bool(fp8)), int(bool(minority))))
     return _GRID_CACHE[key]
 
 
@@ -210,7 +231,8 @@ def _sample_moments(X: torch.Tensor, sample_rows: int):
 
 def scaler_fit_cast(X: torch.Tensor, labels: torch.Tensor | None, out: torch.Tensor, comm=None,
                     pivot: torch.Tensor | None = None, bias_value: float = 1.0,
-                    fp8_scale: float = DEFAULT_FP8_SCALE, out_idx: torch.Tensor | None = None) -> ScalerStats:
+                    fp8_scale: float = DEFAULT_FP8_SCALE, out_idx: torch.Tensor | None = None,
+                    minority: "MinorityRows | None" = None, defer_finalize: bool = False) -> ScalerStats:
     """StandardScaler.fit fused with the row cast: ONE read of X yields the (all-reduced)
     statistics and the training rows in ``out`` [n, 32] (col 30 = bias_value, col 31 = label):
       * bf16: pivot-shifted rows s = x - pivot;
@@ -224,7 +246,13 @@ def scaler_fit_cast(X: torch.Tensor, labels: torch.Tensor | None, out: torch.Ten
     written to out[out_idx[i]], e.g. the fold-sorted training table of a CV job straight from the
     raw table.  X is still read in order (a gather of the 120-byte raw rows ran at a third of the
     streaming rate: 772 vs 256 us at 8M rows, profiles/r4_i/timeline_cv_job.txt); the statistics are
-    those of the in-order pass."""
+    those of the in-order pass.
+    ``minority`` (``minority_rows_async(labels)``; device, one process, no ``out_idx``): the pass
+    also writes the RAW rows whose label matches, in row order, into ``minority.xraw`` (padded:
+    zeros past d, col 30 = bias_value, col 31 = label), dropping rows past its capacity; ``out`` and
+    the statistics are bitwise what they are without it.
+    ``defer_finalize`` (device, one process): return stats whose finalize launch is still owed
+    (``ScalerStats.pending``) -- the fused k-NN prep folds it in."""
     _check_X(X)
     idx = out_idx
     if idx is not None:
@@ -238,6 +266,9 @@ def scaler_fit_cast(X: torch.Tensor, labels: torch.Tensor | None, out: torch.Ten
     if labels is not None and (labels.dtype != torch.uint8 or labels.shape[0] != X.shape[0]):
         raise ValueError("labels must be uint8 [n] aligned with X")
     dist = comm is not None and comm.world_size > 1
+    if minority is not None and (dist or idx is not None or not X.is_cuda or labels is None
+                                 or minority.pending.labels is not labels):
+        raise ValueError("minority output: one process, device rows, no out_idx, the labels the rows were counted from")
     colscale = None
     if fp8:
         pivot_fp8, colscale = fp8_fused_prescale(X, comm)  # a sample of X: any order of its rows
@@ -268,7 +299,7 @@ def scaler_fit_cast(X: torch.Tensor, labels: torch.Tensor | None, out: torch.Ten
         m = native()
         piv = _pivot_dev(pivot, d, X.device)
         # all blocks resident at once (occupancy-derived), never more than the tiles
-        nb = max(1, min(_stats_cast_grid(m, X.device, fp8), (n + 127) // 128))
+        nb = max(1, min(_stats_cast_grid(m, X.device, fp8, minority is not None), (n + 127) // 128))
         # block partials, then >= 1 row for the first-level reduce output
         partial = torch.empty((nb + max(1, m.scaler_reduce_scratch_rows(nb))) * 64, device=X.device,
                               dtype=torch.float64)
@@ -276,8 +307,12 @@ def scaler_fit_cast(X: torch.Tensor, labels: torch.Tensor | None, out: torch.Ten
         s = stream_of(X)
         nparts = 1
         if n > 0:
+            mo = minority
             m.scaler_stats_cast(ptr(X), n, d, ptr(piv), ptr(labels), float(bias_value), ptr(out), ptr(partial), nb, s,
-                                ptr(colscale), float(fp8_scale) if fp8 else 1.0, ptr(idx))
+                                ptr(colscale), float(fp8_scale) if fp8 else 1.0, ptr(idx),
+                                *(() if mo is None else (ptr(mo.pending.counts), ptr(mo.pending.tinfo), ptr(mo.pending.tmask),
+                                                         ptr(mo.xraw),
+                                                         int(mo.cap), int(mo.pending.target))))
             if dist:  # the all-reduce needs the one [64] sums vector
                 m.scaler_reduce(ptr(partial), nb, ptr(sums), s)
             else:  # first level only: the finalize kernel sums its rows (one launch fewer)
@@ -292,7 +327,7 @@ def scaler_fit_cast(X: torch.Tensor, labels: torch.Tensor | None, out: torch.Ten
         st = scaler_finalize(sums, None, pivot, d, want_aff=True, colscale=colscale)
     else:
         st = scaler_finalize(sums, float(n), pivot, d, want_aff=True, colscale=colscale,
-                             nparts=nparts if X.is_cuda else 1)
+                             nparts=nparts if X.is_cuda else 1, defer=defer_finalize and X.is_cuda)
     # fp8: stored v = s * k  ->  z = (s - c) * inv = (v - k c) * (inv / k), folded in the finalize
     return st
 
@@ -355,14 +390,18 @@ class PendingCompaction:
         cls._next += 1
         prev = cls._owners[slot]
         if prev is not None:
-            prev.result()
+            prev.count()
         cls._owners[slot] = None
         cls._views[slot][0] = -1
         return slot, cls._dev[slot]
 
-    def __init__(self, labels, target, nb, counts, total, slot: int, side: bool = False, home=None):
+    def __init__(self, labels, target, nb, counts, total, slot: int, side: bool = False, home=None, tinfo=None):
         cls = PendingCompaction
         self.labels, self.target, self.nb, self.counts = labels, target, nb, counts
+        # per-tile form (minority_rows_async): counts are per block of 256 tiles, not per range of
+        # compact_write's grid, and tinfo holds each tile's (prefix | count << 16)
+        self.tinfo = tinfo
+        self._cnt = None
         # the stream the index list belongs to (its consumers run there): result() enqueues the
         # write there whichever stream is current when it is called -- e.g. when a later
         # compaction settles this one from inside its side-stream context
@@ -405,14 +444,27 @@ class PendingCompaction:
             self._drain()
         return int(v[0])
 
+    def count(self) -> int:
+        """The number of matching rows alone: spins on the mapped word like ``result()`` but
+        enqueues nothing (the fused minority chain needs no index list)."""
+        if self._cnt is None:
+            self._cnt = self._count()
+            if PendingCompaction._owners[self._slot] is self:
+                PendingCompaction._owners[self._slot] = None
+            if not self.side:
+                self.total = None
+        return self._cnt
+
     def result(self) -> torch.Tensor:
         if self._out is None:
-            cnt = self._count()
+            cnt = self.count()
+            if self.tinfo is not None:  # per-tile counts do not fit compact_write's ranges: count again
+                with torch.cuda.stream(self.home):
+                    self._out = compact_indices_async(self.labels, self.target).result()
+                return self._out
             with torch.cuda.stream(self.home):
                 if self.side:  # counts were written on the side stream
                     self.home.wait_event(self.event)
-                if PendingCompaction._owners[self._slot] is self:
-                    PendingCompaction._owners[self._slot] = None
                 self.total = None
                 out = torch.empty(cnt, device=self.labels.device, dtype=torch.int64)
                 if cnt:
@@ -470,6 +522,73 @@ def compact_indices_async(labels: torch.Tensor, target: int = 1, nblocks: int = 
         pend = PendingCompaction(labels, target, nb, counts, total, slot, side=True, home=compute)
     counts.record_stream(compute)  # result() launches the index write on the compute stream
     return pend
+
+
+MINORITY_CAP_FLOOR = 4096
+_TILE_SCAN_MAX = 4096  # entries of the small scan: 4096 blocks x 256 tiles x 128 rows
+
+
+def minority_capacity(n: int) -> int:
+    """Rows of the fused pass's minority buffer: n / 64 (1.6 % of the rows; the bench's rate is
+    0.17 %) with a floor.  Balanced data overflows it and takes the index-list chain."""
+    return max(MINORITY_CAP_FLOOR, int(n) // 64)
+
+
+def minority_fusable(labels: torch.Tensor) -> bool:
+    """The per-tile count reads 16-byte label groups and the small scan takes 4096 block counts."""
+    return (labels.is_cuda and labels.dtype == torch.uint8 and labels.dim() == 1 and labels.is_contiguous()
+            and labels.data_ptr() % 16 == 0 and 0 < labels.shape[0] <= _TILE_SCAN_MAX * 256 * 128)
+
+
+@dataclass
+class MinorityRows:
+    """The fused scaler pass's minority-row output: ``pending`` (per-tile count + scan, enqueued in
+    front of the pass) and the raw-row buffer ``xraw`` [cap, 32] fp32 the pass fills."""
+
+    pending: "PendingCompaction"
+    xraw: torch.Tensor
+    cap: int
+
+    def count(self) -> int:
+        return self.pending.count()
+
+    def rows(self) -> torch.Tensor | None:
+        """xraw[:count], or None when the count overflowed the buffer (rows past it were dropped)."""
+        c = self.count()
+        return self.xraw[:c] if c <= self.cap else None
+
+
+def minority_rows_async(labels: torch.Tensor, target: int = 1, cap: int | None = None,
+                        xraw: torch.Tensor | None = None) -> MinorityRows:
+    """Enqueue the per-tile minority count (one thread per 128-row tile of the fused pass) and the
+    scan of its block totals -- the total lands in a mapped pinned word as with
+    ``compact_indices_async`` -- and allocate the raw-row buffer.  Pass the result to
+    ``scaler_fit_cast(minority=...)``."""
+    if not minority_fusable(labels):
+        raise ValueError("labels must be a non-empty contiguous 16-byte aligned uint8 device vector")
+    m = native()
+    n = labels.shape[0]
+    dev = labels.device
+    cap = minority_capacity(n) if cap is None else int(cap)
+    if xraw is None:
+        xraw = torch.empty((cap, NCOLS), device=dev, dtype=torch.float32)
+    if xraw.dtype != torch.float32 or xraw.dim() != 2 or xraw.shape[1] != NCOLS or xraw.shape[0] < cap \
+            or not xraw.is_contiguous() or xraw.device != dev:
+        raise ValueError("xraw must be a contiguous fp32 [>= cap, 32] tensor on the labels' device")
+    nb = int(m.compact_count_tiles_blocks(n))
+    counts = torch.empty(nb, device=dev, dtype=torch.int64)
+    total = torch.empty(1, device=dev, dtype=torch.int64)
+    # per tile: (prefix | count << 16), then the 128-bit label match mask (one allocation)
+    nt = (n + 127) // 128
+    tbuf = torch.empty(4 * nt + (nt + 3) // 4 * 4, device=dev, dtype=torch.int32)
+    tmask, tinfo = tbuf[: 4 * nt], tbuf[4 * nt:]
+    s = stream_of(labels)
+    slot, hdev = PendingCompaction.take_slot()
+    m.compact_count_tiles(ptr(labels), n, target, ptr(counts), ptr(tinfo), ptr(tmask), s)
+    m.exclusive_scan_small(ptr(counts), nb, ptr(total), s, hdev)
+    pend = PendingCompaction(labels, target, nb, counts, total, slot, tinfo=tinfo)
+    pend.tmask = tmask
+    return MinorityRows(pend, xraw, cap)
 
 
 def compact_indices(labels: torch.Tensor, target: int = 1, nblocks: int = 512) -> torch.Tensor:
