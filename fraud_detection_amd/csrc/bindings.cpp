@@ -977,6 +977,15 @@ PYBIND11_MODULE(_fdx_native, m) {
                             P<const float>(leaf), depth, P<float>(margin), P<const uint8_t>(label), spw, gscale,
                             hscale, P<uint32_t>(gh), S(s));
   });
+  m.def("gbdt_eval", [](u margin, u label, int64_t r0, int64_t r1, u rec, u s) {
+    fdx::launch_gbdt_eval(P<const float>(margin), P<const uint8_t>(label), r0, r1, P<long long>(rec), S(s));
+  });
+  m.def("gbdt_eval_walk", [](u binsT, int64_t ldt, int64_t n, u feat, u bin, u leaf, int depth, u margin, u label,
+                             u rec, u s) {
+    fdx::launch_gbdt_eval_walk(P<const uint8_t>(binsT), ldt, n, P<const int>(feat), P<const int>(bin),
+                               P<const float>(leaf), depth, P<float>(margin), P<const uint8_t>(label),
+                               P<long long>(rec), S(s));
+  });
   m.def("gbdt_predict", [](u X, int64_t n, int ld, int d, u feat, u thr, u leaf, int ntrees, int depth, float base,
                            u out, u s) {
     fdx::launch_gbdt_predict(P<const float>(X), n, ld, d, P<const int>(feat), P<const float>(thr), P<const float>(leaf),

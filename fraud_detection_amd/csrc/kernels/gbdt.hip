@@ -1111,6 +1111,89 @@ __global__ __launch_bounds__(256) void gbdt_margin_kernel(const uint8_t* __restr
   }
 }
 
+// ---- per-round evaluation --------------------------------------------------------------------
+// One boosting round's validation record, int64 [4] = (loss_q, n_err, n_pos, n_rows), ADDED into
+// `rec` (the caller zeroes the history once):
+//   loss_q = sum over rows of rint(loss * 2^30), loss = min(softplus(y ? -m : m), -ln(1e-16)) in fp64
+//            (softplus(z) = max(z, 0) + log1p(exp(-|z|)); the cap is xgboost's eps = 1e-16 clamp on p);
+//   n_err  = rows with (m > 0) != (y != 0) (confusion_counts' convention at threshold 0).
+//  * WALK = false: rows [r0, r1) of a margin / label pair the training walk already updated (a
+//    cross-validation fold's hole): 5 bytes read per row.
+//  * WALK = true: an external eval set with its own feature-major bins and margin: the round's new
+//    tree is walked with the partition's goes_right, the leaf added to the margin with
+//    gbdt_margin_kernel<false>'s float32 arithmetic (so the margins are bitwise that kernel's), and
+//    the metrics taken from the updated margin -- one pass instead of a margin walk plus a reduction.
+// Every term is an integer: a thread accumulates its rows, the wave sums by xor shuffles, the
+// block's 4 waves meet in LDS and ONE 64-bit integer atomic per counter per block lands in `rec`.
+// Integer sums do not depend on the order, so the record is bitwise reproducible and ranks merge
+// by addition.  A row's term is < 36.85 * 2^30 < 2^36, so 2^27 rows stay below 2^63 (the launcher
+// checks).  The per-row cost is the fp64 exp + log1p, not the 5 bytes, so the grid is sized for
+// VALU occupancy and few atomics: 4 rows per thread before the grid stops growing, at most 4
+// blocks (16 waves) per CU -- <= 4 * CUs same-address atomics per counter per launch.
+constexpr int kEvalThreads = 256;
+constexpr int kEvalRowsPerThread = 4;
+constexpr int kEvalBlocksPerCU = 4;
+constexpr int64_t kEvalMaxRows = (int64_t)1 << 27;
+constexpr double kEvalLossCap = 36.841361487904734;  // -ln(1e-16)
+constexpr double kEvalLossScale = 1073741824.0;      // 2^30
+
+__device__ __forceinline__ long long eval_loss_q(float margin, bool pos) {
+  const double m = (double)margin;
+  const double z = pos ? -m : m;
+  const double sp = fmax(z, 0.0) + log1p(exp(-fabs(z)));
+  return (long long)rint(fmin(sp, kEvalLossCap) * kEvalLossScale);
+}
+
+template <bool WALK>
+__global__ __launch_bounds__(kEvalThreads) void gbdt_eval_kernel(
+    float* __restrict__ margin, const uint8_t* __restrict__ label, int64_t r0, int64_t r1,
+    const uint8_t* __restrict__ binsT, int64_t ldt, const int* __restrict__ feat, const int* __restrict__ bin,
+    const float* __restrict__ leaf, int depth, unsigned long long* __restrict__ rec) {
+  __shared__ int sf[kGBMaxNodes], sb[kGBMaxNodes];
+  __shared__ float sl[kGBMaxNodes + 1];
+  __shared__ long long red[kEvalThreads / kWave][4];
+  const int ni = WALK ? heap_first(depth) : 0;
+  if constexpr (WALK) {
+    for (int i = threadIdx.x; i < ni; i += blockDim.x) {
+      sf[i] = feat[i];
+      sb[i] = bin[i];
+    }
+    for (int i = threadIdx.x; i <= ni; i += blockDim.x) sl[i] = leaf[i];
+    __syncthreads();
+  }
+  long long loss = 0;
+  int err = 0, npos = 0, rows = 0;  // <= 2^27 rows in all: a thread's counts fit an int
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t r = r0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < r1; r += stride) {
+    float m = margin[r];
+    if constexpr (WALK) {
+      int node = 0;
+      for (int l = 0; l < depth; ++l) node = 2 * node + 1 + (int)goes_right(binsT, ldt, r, node, sf, sb);
+      m = m + sl[node - ni];
+      margin[r] = m;
+    }
+    const bool pos = label[r] != 0;
+    loss += eval_loss_q(m, pos);
+    err += (int)((m > 0.0f) != pos);
+    npos += (int)pos;
+    rows += 1;
+  }
+  long long v[4] = {loss, (long long)err, (long long)npos, (long long)rows};
+#pragma unroll
+  for (int c = 0; c < 4; ++c) v[c] = wave_sum(v[c]);
+  if (lane_id() == 0) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) red[wave_id()][c] = v[c];
+  }
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    long long s = 0;
+#pragma unroll
+    for (int w = 0; w < kEvalThreads / kWave; ++w) s += red[w][threadIdx.x];
+    if (s != 0) atomicAdd(rec + threadIdx.x, (unsigned long long)s);
+  }
+}
+
 // ---- inference on fp32 rows ------------------------------------------------------------------
 // One thread per row; the row sits in LDS (dynamic feature index without scratch), the trees of
 // the current chunk in LDS; every row walks exactly `depth` levels per tree.
@@ -1316,6 +1399,36 @@ void launch_gbdt_margin(const uint8_t* binsT, int64_t ldt, int64_t n, const int*
     gbdt_margin_kernel<false><<<grid, 256, 0, stream>>>(binsT, ldt, n, feat, bin, leaf, depth, margin, label,
                                                         spw, gscale, hscale, gh);
   check_launch("gbdt_margin");
+}
+
+template <bool WALK>
+static int gbdt_eval_grid(int64_t rows) {
+  static const int resident = resident_cap(gbdt_eval_kernel<WALK>, kEvalThreads);
+  static const int cap = resident < kEvalBlocksPerCU * device_cu_count() ? resident : kEvalBlocksPerCU * device_cu_count();
+  return capped_grid(rows, kEvalThreads * kEvalRowsPerThread, cap);
+}
+
+void launch_gbdt_eval(const float* margin, const uint8_t* label, int64_t r0, int64_t r1, long long* rec,
+                      hipStream_t stream) {
+  if (r0 < 0 || r1 < r0) throw std::runtime_error("gbdt_eval: bad row range");
+  if (r1 - r0 > kEvalMaxRows) throw std::runtime_error("gbdt_eval: at most 2^27 eval rows (int64 loss sum)");
+  if (r1 == r0) return;
+  gbdt_eval_kernel<false><<<gbdt_eval_grid<false>(r1 - r0), kEvalThreads, 0, stream>>>(
+      const_cast<float*>(margin), label, r0, r1, nullptr, 0, nullptr, nullptr, nullptr, 0,
+      reinterpret_cast<unsigned long long*>(rec));
+  check_launch("gbdt_eval");
+}
+
+void launch_gbdt_eval_walk(const uint8_t* binsT, int64_t ldt, int64_t n, const int* feat, const int* bin,
+                           const float* leaf, int depth, float* margin, const uint8_t* label, long long* rec,
+                           hipStream_t stream) {
+  if (depth < 1 || depth > 7) throw std::runtime_error("gbdt_eval_walk: depth must be in [1, 7]");
+  if (n < 0 || n > ldt) throw std::runtime_error("gbdt_eval_walk: rows exceed the bins' leading dimension");
+  if (n > kEvalMaxRows) throw std::runtime_error("gbdt_eval_walk: at most 2^27 eval rows (int64 loss sum)");
+  if (n == 0) return;
+  gbdt_eval_kernel<true><<<gbdt_eval_grid<true>(n), kEvalThreads, 0, stream>>>(
+      margin, label, 0, n, binsT, ldt, feat, bin, leaf, depth, reinterpret_cast<unsigned long long*>(rec));
+  check_launch("gbdt_eval_walk");
 }
 
 void launch_gbdt_predict(const float* X, int64_t n, int ld, int d, const int* feat, const float* thr,

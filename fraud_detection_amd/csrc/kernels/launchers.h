@@ -463,6 +463,14 @@ void launch_gbdt_leaf(const long long* ng, const long long* nh, int depth, doubl
 void launch_gbdt_margin(const uint8_t* binsT, int64_t ldt, int64_t n, const int* feat, const int* bin,
                         const float* leaf, int depth, float* margin, const uint8_t* label, float spw, float gscale,
                         float hscale, uint32_t* gh, hipStream_t stream);
+// One round's validation record added into rec = int64 [4] (loss_q, n_err, n_pos, n_rows), exact
+// integers (gbdt.hip gbdt_eval_kernel): over rows [r0, r1) of an up-to-date margin, or (walk) over
+// an external eval set whose margin first takes the round's tree.  At most 2^27 rows.
+void launch_gbdt_eval(const float* margin, const uint8_t* label, int64_t r0, int64_t r1, long long* rec,
+                      hipStream_t stream);
+void launch_gbdt_eval_walk(const uint8_t* binsT, int64_t ldt, int64_t n, const int* feat, const int* bin,
+                           const float* leaf, int depth, float* margin, const uint8_t* label, long long* rec,
+                           hipStream_t stream);
 void launch_gbdt_predict(const float* X, int64_t n, int ld, int d, const int* feat, const float* thr,
                          const float* leaf, int ntrees, int depth, float base_margin, float* out,
                          hipStream_t stream);

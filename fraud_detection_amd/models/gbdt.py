@@ -45,16 +45,24 @@ def _as_tensor(X, device=None, dtype=torch.float32) -> torch.Tensor:
 class GBDTClassifier:
     def __init__(self, n_estimators: int = 100, learning_rate: float = 0.1, max_depth: int = 5,
                  reg_lambda: float = 1.0, min_child_weight: float = 1.0, gamma: float = 0.0, max_bin: int = 256,
-                 scale_pos_weight: float = 1.0, base_score: float = 0.5, device: str = "auto", **_ignored):
-        # xgboost-only knobs the reference passes (objective, eval_metric, random_state, n_jobs)
-        # are accepted and ignored: the objective is binary:logistic, the fit is deterministic.
+                 scale_pos_weight: float = 1.0, base_score: float = 0.5, device: str = "auto",
+                 eval_metric=None, early_stopping_rounds: int | None = None, **_ignored):
+        # xgboost-only knobs the reference passes (objective, random_state, n_jobs) are accepted and
+        # ignored: the objective is binary:logistic, the fit is deterministic.  eval_metric and
+        # early_stopping_rounds are constructor arguments as in xgboost >= 1.6; they act only when
+        # fit() gets an eval_set (the reference's call passes none: nothing is evaluated).
         self.params = gb.GBDTParams(n_estimators=n_estimators, learning_rate=learning_rate, max_depth=max_depth,
                                     reg_lambda=reg_lambda, min_child_weight=min_child_weight, gamma=gamma,
                                     max_bin=max_bin, scale_pos_weight=scale_pos_weight, base_score=base_score)
         self.device = device
+        self.eval_metric = eval_metric
+        self.early_stopping_rounds = early_stopping_rounds
         self.ensemble: gb.TreeEnsemble | None = None
         self._dens = None
         self.feature_names_in_ = None
+        self.evals_result_: dict | None = None
+        self.best_iteration: int | None = None
+        self.best_score: float | None = None
 
     def _dev(self, X):
         if isinstance(X, torch.Tensor) and self.device == "auto":
@@ -75,34 +83,77 @@ class GBDTClassifier:
     def __setstate__(self, st):
         st = dict(st)
         st["params"] = gb.GBDTParams(**{k: v for k, v in st["params"].items() if k in _PARAM_FIELDS})
+        # models pickled before evaluation existed carry none of its attributes
+        for k in ("eval_metric", "early_stopping_rounds", "evals_result_", "best_iteration", "best_score"):
+            st.setdefault(k, None)
         self.__dict__.update(st)
 
-    def fit(self, X, y, comm=None):
+    def fit(self, X, y, comm=None, eval_set=None, verbose: bool = False):
+        """``eval_set``: ``[(Xv, yv)]`` (exactly one set, xgboost's list form) evaluated after every
+        round with the constructor's ``eval_metric`` (a name or a list; default "logloss"); with
+        ``early_stopping_rounds`` the last metric stops the fit and the model keeps trees
+        [: best_iteration + 1] (xgboost keeps the tail and never predicts with it).  Without
+        ``eval_set`` nothing is evaluated."""
         dev = self._dev(X)
         Xt = _as_tensor(X, dev)
         yt = (y if isinstance(y, torch.Tensor) else torch.from_numpy(np.asarray(y))).to(dev).to(torch.uint8)
-        self.ensemble = gb.fit(Xt, yt.contiguous(), self.params, comm=comm)
         self._dens = None
+        self.evals_result_, self.best_iteration, self.best_score = None, None, None
+        if eval_set is None:
+            if self.early_stopping_rounds is not None:
+                raise ValueError("early_stopping_rounds needs fit(..., eval_set=[(Xv, yv)])")
+            self.ensemble = gb.fit(Xt, yt.contiguous(), self.params, comm=comm)
+            return self
+        if isinstance(eval_set, tuple):
+            eval_set = [eval_set]
+        if len(eval_set) != 1:
+            raise ValueError("exactly one eval set is supported")
+        Xv, yv = eval_set[0]
+        Xv = _as_tensor(Xv, dev)
+        yv = (yv if isinstance(yv, torch.Tensor) else torch.from_numpy(np.asarray(yv))).to(dev).to(torch.uint8)
+        metrics = self.eval_metric if self.eval_metric is not None else "logloss"
+        self.ensemble, rec = gb.fit(Xt, yt.contiguous(), self.params, comm=comm, eval_set=(Xv, yv.contiguous()),
+                                    eval_metric=metrics, early_stopping_rounds=self.early_stopping_rounds)
+        self.evals_result_ = {"validation_0": {k: list(v) for k, v in rec.history.items()}}
+        self.best_iteration, self.best_score = rec.best_iteration, rec.best_score
+        if verbose:
+            for t in range(rec.n_rounds):
+                print(f"[{t}]\t" + "\t".join(f"validation_0-{k}:{v[t]:.5f}" for k, v in rec.history.items()))
         return self
+
+    def evals_result(self) -> dict:
+        """``{"validation_0": {metric: [value per round]}}`` of the last fit with an eval_set."""
+        if self.evals_result_ is None:
+            raise RuntimeError("no evaluation was run: pass eval_set to fit()")
+        return self.evals_result_
 
     def _check(self):
         if self.ensemble is None:
             raise RuntimeError("model is not fitted")
 
-    def predict_margin(self, X) -> np.ndarray:
+    def _n_trees(self, iteration_range):
+        """Trees a predict call uses: all of the (kept) ensemble, or the first k of (0, k)."""
+        if iteration_range is None:
+            return None
+        lo, hi = (int(v) for v in iteration_range)
+        if lo != 0:
+            raise ValueError("iteration_range must start at 0")
+        return self.ensemble.n_trees if hi == 0 else hi  # (0, 0) means every tree, as in xgboost
+
+    def predict_margin(self, X, iteration_range=None) -> np.ndarray:
         self._check()
         dev = self._dev(X)
         Xt = _as_tensor(X, dev)
         if Xt.is_cuda and (self._dens is None or self._dens.device != Xt.device):
             self._dens = gb.DeviceEnsemble(self.ensemble, Xt.device)
-        return gb.predict_margin(Xt, self.ensemble, self._dens).cpu().numpy()
+        return gb.predict_margin(Xt, self.ensemble, self._dens, n_trees=self._n_trees(iteration_range)).cpu().numpy()
 
-    def predict_proba(self, X) -> np.ndarray:
-        p = 1.0 / (1.0 + np.exp(-self.predict_margin(X).astype(np.float64)))
+    def predict_proba(self, X, iteration_range=None) -> np.ndarray:
+        p = 1.0 / (1.0 + np.exp(-self.predict_margin(X, iteration_range).astype(np.float64)))
         return np.stack([1.0 - p, p], 1)
 
-    def predict(self, X) -> np.ndarray:
-        return (self.predict_margin(X) > 0.0).astype(np.int64)
+    def predict(self, X, iteration_range=None) -> np.ndarray:
+        return (self.predict_margin(X, iteration_range) > 0.0).astype(np.int64)
 
     @property
     def feature_importances_(self) -> np.ndarray:

@@ -53,6 +53,11 @@ class GBDTCVResult:
     prep_ms: float = 0.0                           # fold codes, permutation, scaler, cuts, binning
     total_ms: float = 0.0                          # wall clock, whole job incl. the test AUC
     fold_rows: list = field(default_factory=list)  # rows each fold's trees were fit on (real + SMOTE)
+    # with eval_metric: each fold's ops/gbdt.EvalRecord on its own block, its best round, and the
+    # rounds of the final fit (round(mean(best_iteration + 1)) under early stopping)
+    fold_evals: list = field(default_factory=list)
+    fold_best_iteration: list = field(default_factory=list)
+    final_n_estimators: int | None = None
 
     @property
     def cv_auc_mean(self) -> float:
@@ -68,7 +73,17 @@ class DeviceGBDTCV:
     GBDT family on one GPU, on one binned fold-sorted table."""
 
     def __init__(self, cfg: TrainConfig | None = None, params: gb.GBDTParams | None = None, n_folds: int = 5,
-                 seed: int = 42, scale_pos_weight: float | str = "auto"):
+                 seed: int = 42, scale_pos_weight: float | str = "auto", eval_metric=None,
+                 early_stopping_rounds: int | None = None):
+        """``eval_metric`` (a name or a list of "logloss", "error", "auc"): every fold is evaluated on
+        its own block after each round (ops/gbdt.fit_binned eval_set="hole").  With
+        ``early_stopping_rounds`` each fold stops by the last metric and keeps its best trees, the
+        fold AUCs are those of the kept trees, and the final fit grows round(mean(best_iteration + 1))
+        trees instead of ``n_estimators``.  Without either the job is unchanged."""
+        if early_stopping_rounds is not None and eval_metric is None:
+            eval_metric = "logloss"
+        self.eval_metric = eval_metric
+        self.early_stopping_rounds = early_stopping_rounds
         self.cfg = cfg or TrainConfig()
         self.params = params or gb.GBDTParams()
         self.n_folds = int(n_folds)
@@ -132,7 +147,7 @@ class DeviceGBDTCV:
         self.bins, self.labels, self.perm, self.bounds, self.cuts, self.stats = bins, lab, perm, bounds, cuts, stats
         self.fit_rows = []
 
-        def one_fit(k: int | None):
+        def one_fit(k: int | None, n_estimators: int | None = None):
             """Fold k (None: the final fit on the whole split) -> (ensemble, margins of every table row)."""
             if k is None:
                 hole, xmin = (0, 0), xpos
@@ -150,22 +165,35 @@ class DeviceGBDTCV:
                 knn_ops.smote_generate(xmin, nbr, 0, n_new, syn[:n_new], seed=cfg.seed)
                 gb.bin_rows(syn[:n_new, :d], cuts[0], cuts[1], out=bins[n:n + n_new])
             spw = self._spw(float(n_tr - n_min), float(n_min), float(n_min + n_new))
-            params = gb.GBDTParams(**{**p.__dict__, "scale_pos_weight": spw})
-            ens, margin = gb.fit_binned(bins[:n + n_new], lab[:n + n_new], cuts, params, hole=hole,
-                                        return_margin=True)
+            params = gb.GBDTParams(**{**p.__dict__, "scale_pos_weight": spw,
+                                      **({} if n_estimators is None else {"n_estimators": n_estimators})})
+            rec = None
+            if k is not None and self.eval_metric is not None and hole[1] > 0:
+                ens, margin, rec = gb.fit_binned(bins[:n + n_new], lab[:n + n_new], cuts, params, hole=hole,
+                                                 return_margin=True, eval_set="hole", eval_metric=self.eval_metric,
+                                                 early_stopping_rounds=self.early_stopping_rounds)
+            else:
+                ens, margin = gb.fit_binned(bins[:n + n_new], lab[:n + n_new], cuts, params, hole=hole,
+                                            return_margin=True)
             self.fit_rows.append((hole, n_new))
+            self.last_eval = rec
             return ens, margin, n_tr + n_new, n_min, n_new, spw
 
         self._one_fit = one_fit  # tests: refit one fold against the same table
-        aucs, fold_rows = [], []
+        aucs, fold_rows, fold_evals = [], [], []
         for k in range(K):
             _, margin, n_fit, _, _, _ = one_fit(k)
             b0, b1 = int(bounds[k]), int(bounds[k + 1])
             auc, _ = metric_ops.auc_known_positives(margin[b0:b1].contiguous(), lab[b0:b1], pos[k])
             aucs.append(auc)
             fold_rows.append(n_fit)
+            if self.last_eval is not None:
+                fold_evals.append(self.last_eval)
             ev[2 + k].record()
-        ens, _, n_fit, n_min, n_new, spw = one_fit(None)
+        final_T = None
+        if self.early_stopping_rounds is not None and fold_evals:
+            final_T = int(round(float(np.mean([r.best_iteration + 1 for r in fold_evals]))))
+        ens, _, n_fit, n_min, n_new, spw = one_fit(None, final_T)
         ev[2 + K].record()
         final = GBDTResult(scaler=stats, ensemble=ens, n_rows=n, n_train_rows=n_fit, n_minority=n_min,
                            n_synthetic=n_new, scale_pos_weight=spw)
@@ -177,4 +205,6 @@ class DeviceGBDTCV:
         return GBDTCVResult(fold_aucs=fold_aucs, final=final, test_auc=test_auc,
                             fold_ms=[ev[1 + k].elapsed_time(ev[2 + k]) for k in range(K)],
                             final_ms=ev[1 + K].elapsed_time(ev[2 + K]), prep_ms=ev[0].elapsed_time(ev[1]),
-                            total_ms=(time.perf_counter() - t_wall) * 1e3, fold_rows=fold_rows)
+                            total_ms=(time.perf_counter() - t_wall) * 1e3, fold_rows=fold_rows,
+                            fold_evals=fold_evals, fold_best_iteration=[r.best_iteration for r in fold_evals],
+                            final_n_estimators=ens.n_trees if fold_evals else None)

@@ -190,6 +190,150 @@ class _Workspace:
         self.nh = torch.zeros(nheap, dtype=torch.int64, device=dev)
 
 
+# ---- per-round evaluation and early stopping -------------------------------------------------
+EVAL_METRICS = ("logloss", "error", "auc")
+
+
+@dataclass
+class EvalRecord:
+    """What a fit with ``eval_set`` saw on its evaluation rows.
+
+    ``history``: metric name -> one float per round (up to and including the round the fit
+    stopped after); ``records``: the exact int64 [rounds, 4] (loss_q, n_err, n_pos, n_rows) behind
+    them (logloss = loss_q / 2^30 / n_rows, error = n_err / n_rows) and ``twice_pairs`` the AUC's
+    exact pair counts (auc = twice_pairs / (2 P N)).  ``best_iteration`` is the first round with
+    the best value of the LAST metric, ``best_score`` that value."""
+    history: dict
+    best_iteration: int
+    best_score: float
+    metrics: tuple = ("logloss",)
+    records: np.ndarray | None = None
+    twice_pairs: np.ndarray | None = None
+    stopped: bool = False
+
+    @property
+    def n_rounds(self) -> int:
+        return int(self.records.shape[0])
+
+    def to_dict(self) -> dict:
+        return {"history": {k: [float(v) for v in vs] for k, vs in self.history.items()},
+                "best_iteration": int(self.best_iteration), "best_score": float(self.best_score),
+                "stopped": bool(self.stopped)}
+
+
+def stop_round(keys, patience: int | None):
+    """The stop rule on a sequence of exact integer keys (smaller is better): round t improves when
+    its key is strictly below the best so far; the fit stops after the first round t with
+    t - best >= patience.  Returns (best, stop) -- ``stop`` is None when the rule never fires."""
+    best = 0
+    for t in range(1, len(keys)):
+        if keys[t] < keys[best]:
+            best = t
+        elif patience is not None and t - best >= patience:
+            return best, t
+    return best, None
+
+
+class _Eval:
+    """Evaluation state of one fit: the metrics, the exact per-round records and the stop rule.
+    The CPU and the device branch of fit_binned feed it records in round order (``push``) and it
+    answers whether the fit is over -- a pure function of the metric sequence."""
+
+    def __init__(self, metrics, patience, T):
+        self.metrics, self.patience, self.T = metrics, patience, T
+        self.records = np.zeros((T, 4), np.int64)
+        self.twice = np.zeros(T, np.int64)
+        self.done = 0          # records pushed
+        self.best = 0
+        self.stop_at = None    # the round the rule fired after
+
+    @property
+    def want_auc(self) -> bool:
+        return "auc" in self.metrics
+
+    def key(self, t: int) -> int:
+        last = self.metrics[-1]
+        return int(-self.twice[t]) if last == "auc" else int(self.records[t, 0 if last == "logloss" else 1])
+
+    def push(self, rec, twice=0) -> bool:
+        """Record of round ``self.done``; True when the fit stops after that round."""
+        t = self.done
+        self.records[t] = rec
+        self.twice[t] = twice
+        self.done = t + 1
+        if t == 0 or self.key(t) < self.key(self.best):
+            self.best = t
+        elif self.patience is not None and t - self.best >= self.patience:
+            self.stop_at = t
+            return True
+        return False
+
+    @property
+    def n_keep(self) -> int:
+        """Trees the ensemble keeps: all that were grown, or [: best + 1] under early stopping."""
+        return self.best + 1 if (self.patience is not None and self.done) else self.done
+
+    def result(self) -> EvalRecord:
+        k = self.done
+        rec, tw = self.records[:k].copy(), self.twice[:k].copy()
+        rows = np.maximum(rec[:, 3], 1).astype(np.float64)
+        P = rec[:, 2].astype(np.float64)
+        N = rec[:, 3].astype(np.float64) - P
+        hist = {}
+        for name in self.metrics:
+            if name == "logloss":
+                v = rec[:, 0].astype(np.float64) / R.LOSS_SCALE / rows
+            elif name == "error":
+                v = rec[:, 1].astype(np.float64) / rows
+            else:
+                with np.errstate(all="ignore"):
+                    v = np.where((P > 0) & (N > 0), tw.astype(np.float64) / (2.0 * P * N), np.nan)
+            hist[name] = [float(x) for x in v]
+        best_score = hist[self.metrics[-1]][self.best] if k else float("nan")
+        return EvalRecord(history=hist, best_iteration=int(self.best), best_score=float(best_score),
+                          metrics=tuple(self.metrics), records=rec, twice_pairs=tw if self.want_auc else None,
+                          stopped=self.stop_at is not None)
+
+
+def _eval_request(eval_set, eval_metric, early_stopping_rounds, hole_len, checkpoint, dist, T):
+    """Validated (kind, Xv, yv, _Eval) of a fit's evaluation arguments, or None without eval_set."""
+    if eval_set is None:
+        if early_stopping_rounds is not None:
+            raise ValueError("early_stopping_rounds needs an eval_set")
+        return None
+    if checkpoint is not None:
+        raise NotImplementedError("checkpoint= cannot be combined with eval_set: a resumed fit would have to "
+                                  "replay the metric history and the stop rule's state, which is not saved")
+    metrics = (eval_metric,) if isinstance(eval_metric, str) else tuple(eval_metric or ("logloss",))
+    bad = [m for m in metrics if m not in EVAL_METRICS]
+    if bad or not metrics:
+        raise ValueError(f"eval_metric must be among {EVAL_METRICS}, got {bad or metrics}")
+    if "auc" in metrics and dist:
+        raise NotImplementedError("eval_metric 'auc' is not supported under data-parallel training "
+                                  "(pair counts do not add across ranks)")
+    if early_stopping_rounds is not None and int(early_stopping_rounds) < 1:
+        raise ValueError("early_stopping_rounds must be >= 1")
+    patience = None if early_stopping_rounds is None else int(early_stopping_rounds)
+    if isinstance(eval_set, str):
+        if eval_set != "hole":
+            raise ValueError('eval_set is (Xv, yv) or the string "hole"')
+        if not hole_len:
+            raise ValueError('eval_set="hole" needs hole= (the rows left out of the fit)')
+        return "hole", None, None, _Eval(metrics, patience, T)
+    if isinstance(eval_set, list):
+        if len(eval_set) != 1:
+            raise ValueError("exactly one eval set is supported")
+        eval_set = eval_set[0]
+    if not (isinstance(eval_set, tuple) and len(eval_set) == 2):
+        raise ValueError('eval_set is (Xv, yv) or the string "hole"')
+    Xv, yv = eval_set
+    if Xv.shape[0] != yv.shape[0]:
+        raise ValueError("eval_set: Xv and yv disagree on the row count")
+    if Xv.shape[0] > R.EVAL_MAX_ROWS:
+        raise ValueError("at most 2^27 eval rows")
+    return "set", Xv, yv, _Eval(metrics, patience, T)
+
+
 def _resume(checkpoint, sig, T):
     """Trees of a matching checkpoint (numpy arrays) and how many rounds they cover."""
     if checkpoint is None:
@@ -204,13 +348,17 @@ def _resume(checkpoint, sig, T):
 
 def fit(X: torch.Tensor, y: torch.Tensor, params: GBDTParams | None = None, comm=None,
         cuts=None, sample_weight_pos: float | None = None, return_margin: bool = False,
-        checkpoint=None, checkpoint_every: int = 10, use_graph: bool | None = None):
+        checkpoint=None, checkpoint_every: int = 10, use_graph: bool | None = None,
+        eval_set=None, eval_metric=("logloss",), early_stopping_rounds: int | None = None):
     """Boost `n_estimators` depth-D trees on standardized float32 rows X [n, d] with labels y.
 
     ``checkpoint``: a utils.checkpoint.CheckpointManager.  Every ``checkpoint_every`` rounds the
     trees so far are saved; a later call with the same data/config resumes after the last saved
     round.  Training margins are recomputed from the saved trees over the same bins, so a resumed
-    fit is bit-identical to an uninterrupted one."""
+    fit is bit-identical to an uninterrupted one.
+
+    ``eval_set`` / ``eval_metric`` / ``early_stopping_rounds``: see fit_binned; with an eval set
+    the return value gains an EvalRecord as its last element."""
     p = (params or GBDTParams()).validate()
     n, d = X.shape
     if d > MAX_FEAT:
@@ -219,18 +367,36 @@ def fit(X: torch.Tensor, y: torch.Tensor, params: GBDTParams | None = None, comm
         cuts = quantile_cuts(X, p.max_bin, p.cut_sample_rows, comm)
     bins = bin_rows(X, cuts[0], cuts[1])
     return fit_binned(bins, y, cuts, p, comm=comm, sample_weight_pos=sample_weight_pos, return_margin=return_margin,
-                      checkpoint=checkpoint, checkpoint_every=checkpoint_every, use_graph=use_graph)
+                      checkpoint=checkpoint, checkpoint_every=checkpoint_every, use_graph=use_graph,
+                      eval_set=eval_set, eval_metric=eval_metric, early_stopping_rounds=early_stopping_rounds)
 
 
 def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | None = None, comm=None,
                sample_weight_pos: float | None = None, return_margin: bool = False, checkpoint=None,
-               checkpoint_every: int = 10, use_graph: bool | None = None, hole: tuple | None = None):
+               checkpoint_every: int = 10, use_graph: bool | None = None, hole: tuple | None = None,
+               eval_set=None, eval_metric=("logloss",), early_stopping_rounds: int | None = None):
     """Boosting on already-binned rows (u8 [n, 32], bin_rows) with their cuts (cuts, nbins).
 
     ``hole``: (at, len) -- the fit's rows are the table without the block [at, at + len) (a
     cross-validation fold on the fold-sorted table: no per-fold copy).  The returned margin (with
     ``return_margin``) covers EVERY table row, so the block's margins are the fold's validation
-    scores under the fitted ensemble."""
+    scores under the fitted ensemble.
+
+    ``eval_set``: ``(Xv, yv)`` -- standardized float32 rows (binned here with the fit's cuts) or
+    already-binned u8 [m, 32] rows, with uint8 labels -- or the string ``"hole"``: the hole's rows,
+    whose margins every round's walk keeps current anyway.  Exactly one eval set.  After every round
+    the metrics of ``eval_metric`` ("logloss", "error", "auc") are taken on it as exact integers
+    (gbdt.hip gbdt_eval_kernel; EvalRecord).  Without ``early_stopping_rounds`` this changes nothing
+    about the trees.  With it, the LAST metric drives the stop rule (as in xgboost): a round improves
+    when its integer sum is strictly better than the best so far, and the fit stops after the first
+    round t with t - best >= early_stopping_rounds.  The host waits for round t - patience's record
+    before it enqueues round t, so at most ``early_stopping_rounds`` rounds are in flight and the
+    decision does not depend on timing.  The ensemble then keeps trees [: best_iteration + 1] --
+    xgboost keeps the later trees in the booster and merely never predicts with them -- and the
+    returned margin is rebuilt from the kept trees by the round's own margin kernel, so it equals
+    their walk bit for bit.  With an eval set the return value gains an EvalRecord as its last
+    element.  Under data-parallel training every rank passes its shard of the eval rows and the
+    integer records are all-reduced, so all ranks stop at the same round."""
     p = (params or GBDTParams()).validate()
     cuts_np, nbins = cuts
     d = int(len(nbins))
@@ -250,6 +416,23 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
     T = p.n_estimators
     base_margin = float(np.log(p.base_score / (1.0 - p.base_score)))
     ens_kw = dict(depth=D, cuts=cuts_np, nbins=nbins, base_score=p.base_score, params=dict(p.__dict__))
+    req = _eval_request(eval_set, eval_metric, early_stopping_rounds, hl, checkpoint,
+                        comm is not None and comm.world_size > 1, T)
+    ev = None
+    if req is not None:
+        ev_kind, Xv, yv, ev = req
+        if ev_kind == "set":
+            if yv.dtype != torch.uint8 or yv.device != bins.device or Xv.device != bins.device:
+                raise ValueError("eval_set: yv must be uint8, and Xv, yv on the fit's device")
+            if Xv.dtype == torch.uint8:
+                if Xv.dim() != 2 or Xv.shape[1] != R.ROW_BYTES:
+                    raise ValueError("eval_set: binned rows must be u8 [m, 32]")
+                bins_v = Xv.contiguous()
+            else:
+                if Xv.dim() != 2 or Xv.shape[1] != d:
+                    raise ValueError(f"eval_set: the fit has {d} features, Xv has {tuple(Xv.shape)}")
+                bins_v = bin_rows(Xv if Xv.is_cuda else Xv.float(), cuts_np, nbins)
+            yv = yv.contiguous()
     sig = None
     if checkpoint is not None:
         from ..utils.checkpoint import config_signature
@@ -279,6 +462,9 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
         if t0:
             feat[:t0], binv[:t0], thr[:t0], gain[:t0], leaf[:t0] = (prev[k] for k in ("feat", "bin", "thr", "gain", "leaf"))
             margin = R.predict_margin_bins(b, feat[:t0], binv[:t0], leaf[:t0], D, base_margin)
+        if ev is not None:  # the eval rows' bins, labels and running margin (the device's eval walk)
+            b_ev, y_ev = (b_all[ha:ha + hl], y_all[ha:ha + hl]) if ev_kind == "hole" else (bins_v.numpy(), yv.numpy())
+            m_ev = np.full(b_ev.shape[0], np.float32(base_margin), np.float32)
         for t in range(t0, T):
             q = R.gradients(margin, yy, spw, gscale, hscale)
             tr, node = R.build_tree(b, q, cuts_np, nbins, D, p.reg_lambda, p.min_child_weight, p.gamma,
@@ -287,14 +473,27 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
             margin = (margin + tr.leaf[node]).astype(np.float32)
             if (t + 1) % max(1, checkpoint_every) == 0 or t + 1 == T:
                 _save(t + 1, feat, binv, thr, gain, leaf)
+            if ev is not None:
+                m_ev = (m_ev + R.predict_margin_bins(b_ev, feat[t:t + 1], binv[t:t + 1], leaf[t:t + 1], D, 0.0)
+                        ).astype(np.float32)
+                rec = R.eval_record(m_ev, y_ev)
+                if comm is not None and comm.world_size > 1:
+                    rec = comm.all_reduce(torch.from_numpy(rec)).numpy()
+                if ev.push(rec, R.twice_pairs(m_ev, y_ev) if ev.want_auc else 0):
+                    break
+        if ev is not None and ev.n_keep < T:  # early stop: keep [: best + 1], margins of the kept trees
+            k = ev.n_keep
+            feat, binv, thr, gain, leaf = feat[:k], binv[:k], thr[:k], gain[:k], leaf[:k]
+            margin = R.predict_margin_bins(b, feat, binv, leaf, D, base_margin)
         ens = TreeEnsemble(feat=feat, bin=binv, thr=thr, gain=gain, leaf=leaf, **ens_kw)
+        tail = () if ev is None else (ev.result(),)
         if not return_margin:
-            return ens
+            return (ens, *tail) if tail else ens
         full = np.empty(n, np.float32)
         full[keep] = margin
         if hl:
             full[ha:ha + hl] = R.predict_margin_bins(b_all[ha:ha + hl], feat, binv, leaf, D, base_margin)
-        return ens, torch.from_numpy(full)
+        return (ens, torch.from_numpy(full), *tail)
 
     m = native()
     dev = bins.device
@@ -383,10 +582,61 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
     # 0.96M rows and 1.62 vs 1.54 at 6.4M (profiles/r1_s22).
     if use_graph is None:  # opt-in: measured slower than eager launches (profiles/r1_s22)
         use_graph = os.environ.get("FDX_GBDT_GRAPH", "0") == "1"
-    graphable = use_graph and not dist and n > 0 and T - t0 >= 3
-    fuse_margin = os.environ.get("FDX_GBDT_FUSE_MARGIN", "0") == "1" and not graphable
+    # Evaluation keeps the eager launches: a round is followed by the eval kernel, a record copy and
+    # an event, and the stop rule may end the fit between two rounds.  The deferred margin walk is
+    # off too (the hole's margins must be current when the round's record is taken).
+    graphable = use_graph and not dist and n > 0 and T - t0 >= 3 and ev is None
+    fuse_margin = os.environ.get("FDX_GBDT_FUSE_MARGIN", "0") == "1" and not graphable and ev is None
     graph = None
+    if ev is not None:
+        # device history, zeroed once (the kernel adds into a round's row); pinned host mirror the
+        # round's record is copied into on the fit's stream, with one event per round
+        ev_hist = torch.zeros((T, 4), dtype=torch.int64, device=dev)
+        ev_host = torch.empty((T, 4), dtype=torch.int64).pin_memory()
+        ev_done = [None] * T
+        if ev_kind == "set":
+            nv = int(bins_v.shape[0])
+            ldt_v = max(4, (nv + 255) // 256 * 256)
+            binsT_v = torch.empty(d * ldt_v, dtype=torch.uint8, device=dev)
+            if nv:
+                m.gbdt_transpose(ptr(bins_v), nv, d, ptr(binsT_v), ldt_v, st0)
+            m_ev, y_ev = torch.full((nv,), base_margin, dtype=torch.float32, device=dev), yv
+        else:
+            m_ev, y_ev = margin[ha:ha + hl], y[ha:ha + hl]  # views: the training walk keeps them current
+        if ev.want_auc:
+            ev_tw = torch.zeros(T, dtype=torch.int64, device=dev)
+            tw_host = torch.zeros(T, dtype=torch.int64).pin_memory()
+            ev_pos = int(y_ev.sum(dtype=torch.int64).item())  # the positive count, read once
+
+        def eval_round(t):
+            st = stream_of(bins)
+            if ev_kind == "set":
+                m.gbdt_eval_walk(ptr(binsT_v), ldt_v, nv, ptr(feat[t]), ptr(binv[t]), ptr(leaf[t]), D, ptr(m_ev),
+                                 ptr(y_ev), ptr(ev_hist[t]), st)
+            else:
+                m.gbdt_eval(ptr(margin), ptr(y), ha, ha + hl, ptr(ev_hist[t]), st)
+            if dist:
+                comm.all_reduce_(ev_hist[t])
+            ev_host[t].copy_(ev_hist[t], non_blocking=True)
+            if ev.want_auc:
+                from . import metrics as metric_ops
+
+                _, twice = metric_ops.auc_known_positives(m_ev, y_ev, ev_pos)
+                ev_tw[t].copy_(twice)
+                tw_host[t:t + 1].copy_(ev_tw[t:t + 1], non_blocking=True)
+            ev_done[t] = torch.cuda.Event()
+            ev_done[t].record()
+
+        def eval_take(s):
+            """Wait for round s's record and apply the stop rule to it."""
+            ev_done[s].synchronize()
+            return ev.push(ev_host[s].numpy(), int(tw_host[s]) if ev.want_auc else 0)
+
+    rounds_run = t0
     for t in range(t0, T):
+        if ev is not None and ev.patience is not None and t - ev.patience >= 0 and eval_take(t - ev.patience):
+            break
+        rounds_run = t + 1
         if graphable and t == t0 + 1:  # round t0 ran eagerly: its kernels had to execute
             from ..runtime.graphs import capture
 
@@ -408,9 +658,26 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
                        prev=(feat[t - 1], binv[t - 1], leaf[t - 1]) if (fuse and t > t0) else None,
                        defer_margin=fuse and t + 1 < T)
         after_round(t)
-    ens = TreeEnsemble(feat=feat.cpu().numpy(), bin=binv.cpu().numpy(), thr=thr.cpu().numpy(),
-                       gain=gain.cpu().numpy(), leaf=leaf.cpu().numpy(), **ens_kw)
-    return (ens, margin) if return_margin else ens
+        if ev is not None:
+            eval_round(t)
+    if ev is None:
+        ens = TreeEnsemble(feat=feat.cpu().numpy(), bin=binv.cpu().numpy(), thr=thr.cpu().numpy(),
+                           gain=gain.cpu().numpy(), leaf=leaf.cpu().numpy(), **ens_kw)
+        return (ens, margin) if return_margin else ens
+    # the records still in flight, in round order (the rule may fire on one of them: the rounds
+    # enqueued past it are dropped, exactly as if the host had seen the record in time)
+    while ev.stop_at is None and ev.done < rounds_run:
+        eval_take(ev.done)
+    k = ev.n_keep
+    if return_margin and k < rounds_run and n:
+        # margins of the kept trees, by the round's own margin kernel (as the checkpoint resume)
+        margin.fill_(base_margin)
+        for t in range(k):
+            m.gbdt_margin(ptr(binsT), ldt, n, ptr(feat[t]), ptr(binv[t]), ptr(leaf[t]), D, ptr(margin), ptr(y), spw,
+                          gscale, hscale, 0, st0)
+    ens = TreeEnsemble(feat=feat[:k].cpu().numpy(), bin=binv[:k].cpu().numpy(), thr=thr[:k].cpu().numpy(),
+                       gain=gain[:k].cpu().numpy(), leaf=leaf[:k].cpu().numpy(), **ens_kw)
+    return (ens, margin, ev.result()) if return_margin else (ens, ev.result())
 
 
 # ---- inference -------------------------------------------------------------------------------
@@ -425,22 +692,29 @@ class DeviceEnsemble:
         self.leaf = torch.from_numpy(np.ascontiguousarray(ens.leaf)).to(device)
 
 
-def predict_margin(X: torch.Tensor, ens: TreeEnsemble, dens: DeviceEnsemble | None = None) -> torch.Tensor:
-    """float32 margins of standardized rows X [n, d] (d <= 30, any row stride)."""
+def predict_margin(X: torch.Tensor, ens: TreeEnsemble, dens: DeviceEnsemble | None = None,
+                   n_trees: int | None = None) -> torch.Tensor:
+    """float32 margins of standardized rows X [n, d] (d <= 30, any row stride).  ``n_trees``: use
+    only the first n_trees trees (the ensemble after that many boosting rounds)."""
     n, d = X.shape
     if d != ens.n_features:
         raise ValueError(f"model has {ens.n_features} features, X has {d}")
+    k = ens.n_trees if n_trees is None else int(n_trees)
+    if not 0 <= k <= ens.n_trees:
+        raise ValueError(f"n_trees must be in [0, {ens.n_trees}]")
     if not X.is_cuda:
-        return torch.from_numpy(R.predict_margin(X.numpy(), ens.feat, ens.thr, ens.leaf, ens.depth, ens.base_margin))
+        return torch.from_numpy(R.predict_margin(X.numpy(), ens.feat[:k], ens.thr[:k], ens.leaf[:k], ens.depth,
+                                                 ens.base_margin))
     if X.dtype != torch.float32 or X.stride(1) != 1:
         raise ValueError("X must be float32 with unit column stride")
     dens = dens if dens is not None and dens.device == X.device else DeviceEnsemble(ens, X.device)
     out = torch.empty(n, dtype=torch.float32, device=X.device)
     if n:
-        native().gbdt_predict(ptr(X), n, X.stride(0), d, ptr(dens.feat), ptr(dens.thr), ptr(dens.leaf), ens.n_trees,
+        native().gbdt_predict(ptr(X), n, X.stride(0), d, ptr(dens.feat), ptr(dens.thr), ptr(dens.leaf), k,
                               ens.depth, ens.base_margin, ptr(out), stream_of(X))
     return out
 
 
-def predict_proba(X: torch.Tensor, ens: TreeEnsemble, dens: DeviceEnsemble | None = None) -> torch.Tensor:
-    return torch.sigmoid(predict_margin(X, ens, dens))
+def predict_proba(X: torch.Tensor, ens: TreeEnsemble, dens: DeviceEnsemble | None = None,
+                  n_trees: int | None = None) -> torch.Tensor:
+    return torch.sigmoid(predict_margin(X, ens, dens, n_trees))

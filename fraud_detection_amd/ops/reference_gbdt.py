@@ -178,6 +178,37 @@ def build_tree(bins: np.ndarray, q: np.ndarray, cuts: np.ndarray, nbins: np.ndar
     return TreeArrays(feat, binv, thr, gain, leaf), node
 
 
+LOSS_CAP = 36.841361487904734  # -ln(1e-16): xgboost clamps p to [eps, 1 - eps], eps = 1e-16
+LOSS_SCALE = float(2 ** 30)    # fixed point of a row's log-loss
+EVAL_MAX_ROWS = 1 << 27        # 36.85 * 2^30 * 2^27 < 2^63: the int64 loss sum cannot overflow
+
+
+def eval_record(margin: np.ndarray, y: np.ndarray) -> np.ndarray:
+    """int64 [4] = (loss_q, n_err, n_pos, n_rows) of fp32 margins against 0/1 labels -- the oracle
+    of gbdt.hip's gbdt_eval_kernel.  loss_q = sum rint(loss * 2^30) with, per row in fp64,
+    loss = min(softplus(y ? -m : m), -ln(1e-16)), softplus(z) = max(z, 0) + log1p(exp(-|z|));
+    a row is an error when (m > 0) != (y != 0).  All four are exact integers, so records of
+    disjoint row sets add."""
+    m = np.asarray(margin, dtype=np.float32).astype(np.float64).ravel()
+    pos = np.asarray(y).ravel() != 0
+    if m.shape[0] > EVAL_MAX_ROWS:
+        raise ValueError("at most 2^27 eval rows")
+    z = np.where(pos, -m, m)
+    with np.errstate(over="ignore"):
+        sp = np.maximum(z, 0.0) + np.log1p(np.exp(-np.abs(z)))
+    q = np.rint(np.fmin(sp, LOSS_CAP) * LOSS_SCALE).astype(np.int64)
+    return np.array([q.sum(), np.count_nonzero((m > 0.0) != pos), np.count_nonzero(pos), m.shape[0]], dtype=np.int64)
+
+
+def twice_pairs(margin: np.ndarray, y: np.ndarray) -> int:
+    """2 #{s_p > s_n} + #{s_p == s_n} over (positive, negative) pairs: AUC = twice_pairs / (2 P N)."""
+    s = np.asarray(margin, dtype=np.float32).ravel()
+    pos = np.asarray(y).ravel() != 0
+    neg = np.sort(s[~pos])
+    sp = s[pos]
+    return int(np.searchsorted(neg, sp, side="left").sum() + np.searchsorted(neg, sp, side="right").sum())
+
+
 def predict_margin(X: np.ndarray, feat: np.ndarray, thr: np.ndarray, leaf: np.ndarray, depth: int,
                    base_margin: float = 0.0) -> np.ndarray:
     """X [n, d] float32; feat/thr [T, ni]; leaf [T, nl].  float32 margins (sum in tree order)."""

@@ -53,10 +53,15 @@ def _shard(idx: np.ndarray, comm) -> np.ndarray:
 
 
 def run(settings: Settings | None = None, model_type: str = "logistic", cv_folds: int = 5, model_dir: str = "models",
-        verbose: bool = True, cfg: TrainConfig | None = None, comm=None) -> dict:
+        verbose: bool = True, cfg: TrainConfig | None = None, comm=None, gbdt_eval_metric=None,
+        gbdt_early_stopping: int | None = None) -> dict:
     """Single process, or data parallel when ``comm`` spans several ranks (torchrun: one rank per
     GPU).  Every rank reads the table and derives the same split; each fits on its strided shard
-    with RCCL all-reduced statistics, so all ranks hold the same model; rank 0 writes artifacts."""
+    with RCCL all-reduced statistics, so all ranks hold the same model; rank 0 writes artifacts.
+
+    ``gbdt_eval_metric`` / ``gbdt_early_stopping``: per-round validation metrics of every CV fold
+    and early stopping in the device GBDT CV job (models/gbdt_cv.DeviceGBDTCV); the curves, best
+    rounds and the final fit's round count land in the summary under "gbdt_eval"."""
     s = settings or Settings.load()
     comm = comm if (comm is not None and comm.world_size > 1) else None
     lead = comm is None or comm.rank == 0
@@ -110,6 +115,11 @@ def run(settings: Settings | None = None, model_type: str = "logistic", cv_folds
         say(f" Resuming: {len(progress.folds)} completed fold(s) from {progress.path}")
     res_cv = None
     cv_engine = None
+    gbdt_eval = None
+    if (gbdt_eval_metric is not None or gbdt_early_stopping is not None) and not (
+            cv_folds and cv_folds > 1 and pos >= cv_folds and _device_gbdt_cv_ok(model_type, cfg, dev, comm, progress)):
+        raise ValueError("--gbdt-eval-metric / --gbdt-early-stopping need the device GBDT CV job "
+                         "(--model gbdt on one GPU with CV folds, not resumed)")
     if cv_folds and cv_folds > 1 and pos >= cv_folds:
         say(f" Performing Stratified K-Fold Cross-Validation ({cv_folds} folds) with SMOTE inside each fold...")
         if mode == "device":
@@ -147,8 +157,15 @@ def run(settings: Settings | None = None, model_type: str = "logistic", cv_folds
 
             t_fit = time.perf_counter()
             with tracing.span("train.cv_job", model=model_type), tracing.roctx_range("train.cv_job"):
-                cvr = DeviceGBDTCV(cfg, n_folds=cv_folds, seed=42).run(Xtr, ytr, fold_codes=job_codes)
+                cvr = DeviceGBDTCV(cfg, n_folds=cv_folds, seed=42, eval_metric=gbdt_eval_metric,
+                                   early_stopping_rounds=gbdt_early_stopping).run(Xtr, ytr, fold_codes=job_codes)
             cv_scores, res_cv, cv_engine = cvr.fold_aucs, cvr.final, "device"
+            if cvr.fold_evals:
+                gbdt_eval = {"metrics": list(cvr.fold_evals[0].metrics), "early_stopping_rounds": gbdt_early_stopping,
+                             "fold_history": [r.history for r in cvr.fold_evals],
+                             "fold_best_iteration": list(cvr.fold_best_iteration),
+                             "fold_best_score": [r.best_score for r in cvr.fold_evals],
+                             "final_n_estimators": cvr.final_n_estimators}
             for k, auc in enumerate(cv_scores):
                 progress.record(k, auc)
         else:
@@ -196,6 +213,8 @@ def run(settings: Settings | None = None, model_type: str = "logistic", cv_folds
                "cv_auc_std": float(np.std(cv_scores)) if cv_scores else None, "cv_scores": cv_scores,
                "scale_pos_weight": scale_pos_weight, "paths": paths, "device": str(dev), "eval": ev,
                "seconds": round(time.time() - t0, 3), "registered_version": None}
+    if gbdt_eval is not None:
+        summary["gbdt_eval"] = gbdt_eval
     try:
         summary["registered_version"] = _track(s, model_type, res, summary, paths, Xte, names, say)
     except Exception as e:  # noqa: BLE001 - tracking is best effort (reference train_model.py:165-166)
@@ -336,6 +355,14 @@ def _track(s: Settings, model_type, res, summary, paths, Xte, names, say):
         if summary["cv_auc_mean"] is not None:
             mlf.log_metric("cv_auc_mean", summary["cv_auc_mean"])
             mlf.log_metric("cv_auc_std", summary["cv_auc_std"])
+        ge = summary.get("gbdt_eval")
+        if ge:
+            mlf.log_param("gbdt_eval_metric", ",".join(ge["metrics"]))
+            mlf.log_param("gbdt_early_stopping_rounds", ge["early_stopping_rounds"])
+            mlf.log_param("gbdt_final_n_estimators", ge["final_n_estimators"])
+            for k, (best, score) in enumerate(zip(ge["fold_best_iteration"], ge["fold_best_score"])):
+                mlf.log_metric(f"fold{k + 1}_best_iteration", float(best))
+                mlf.log_metric(f"fold{k + 1}_best_{ge['metrics'][-1]}", float(score))
         sample = Xte[:5].cpu().numpy().astype(np.float64)
         if model_type == "logistic":
             model = make_logistic(res.coef, res.intercept, res.fit.n_iter)
@@ -372,6 +399,12 @@ def main(argv=None):
                     help="resume directory: completed CV folds + GBDT tree checkpoints (FDX_CHECKPOINT_DIR)")
     ap.add_argument("--split", default=None, choices=["auto", "sklearn", "device"],
                     help="sklearn: reference-identical split; device: K3 kernel (default auto: device >= 2M rows on GPU)")
+    ap.add_argument("--gbdt-eval-metric", default=None,
+                    help="comma-separated logloss,error,auc: per-round metrics of every CV fold on its own rows "
+                         "(device GBDT CV job); the last one drives early stopping")
+    ap.add_argument("--gbdt-early-stopping", type=int, default=None, metavar="N",
+                    help="stop a fold after N rounds without improvement; the final fit grows "
+                         "round(mean(best_iteration + 1)) trees")
     a = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO)
     comm = None
@@ -386,7 +419,9 @@ def main(argv=None):
     try:
         over = {k: v for k, v in (("split", a.split), ("checkpoint_dir", a.checkpoint_dir)) if v}
         st = Settings.load(**over)
-        out = run(st, model_type=a.model, cv_folds=a.cv_folds, model_dir=a.model_dir, comm=comm)
+        out = run(st, model_type=a.model, cv_folds=a.cv_folds, model_dir=a.model_dir, comm=comm,
+                  gbdt_eval_metric=a.gbdt_eval_metric.split(",") if a.gbdt_eval_metric else None,
+                  gbdt_early_stopping=a.gbdt_early_stopping)
     finally:
         if comm is not None:
             comm.close()
