@@ -1020,6 +1020,19 @@ PYBIND11_MODULE(_fdx_native, m) {
     fdx::launch_auc_radix(P<const float>(scores), P<const uint8_t>(labels), n, P<void>(ws), P<int64_t>(res),
                           P<double>(auc), S(s));
   });
+  m.attr("PR_SCAN_TILE") = fdx::pr_scan_tile();
+  m.attr("PR_TILE_SCAN_THREADS") = fdx::pr_tile_scan_threads();
+  m.def("pr_workspace_bytes", &fdx::pr_workspace_bytes);
+  m.def("pr_layout", [](int64_t n) {
+    size_t off[6];
+    fdx::pr_layout(n, off);
+    return std::vector<size_t>(off, off + 6);
+  });
+  // tp / fp / thr = 0: the curve stays in the workspace (average precision only)
+  m.def("pr_curve", [](u scores, u labels, int64_t n, u ws, u tp, u fp, u thr, u res, u ap, u s) {
+    fdx::launch_pr_curve(P<const float>(scores), P<const uint8_t>(labels), n, P<void>(ws), P<uint32_t>(tp),
+                         P<uint32_t>(fp), P<float>(thr), P<int64_t>(res), P<double>(ap), S(s));
+  });
   m.def("confusion", [](u scores, u labels, int64_t n, float thr, u out4, u s) {
     fdx::launch_confusion(P<const float>(scores), P<const uint8_t>(labels), n, thr, P<unsigned long long>(out4), S(s));
   });

@@ -386,6 +386,165 @@ __global__ void auc_sorted_finalize_kernel(const unsigned long long* __restrict_
   auc[0] = (P > 0 && N > 0) ? (double)twice / (2.0 * (double)P * (double)N) : __builtin_nan("");
 }
 
+// ---- exact precision-recall curve and average precision on the sorted (key, label) arrays -----
+// Descending by score, a tie group g has thr[g], the inclusive cumulative counts TP[g] / FP[g],
+// precision TP / (TP + FP) and recall TP / P (sklearn precision_recall_curve without its appended
+// (1, 0) point);  AP = (1/P) sum_g dtp[g] precision[g] (average_precision_score), taken as the exact
+// integer ap_q = sum_g rint(dtp * (TP / (TP + FP)) * 2^30): one correctly rounded fp64 division and
+// product per term and an int64 sum, so it is order independent and equals the numpy oracle
+// (ops/reference.py average_precision_q).
+// On the ascending sorted rows a row is a group head when its key differs from its predecessor's.
+// A device-wide exclusive scan of the pair (heads, positives), packed into one u64 (both < 2^32),
+// runs as three plain phases with no block waiting on another: per-tile totals -> one block scans
+// the tile totals in place and leaves (G, P) -> the emit kernel recomputes the in-tile prefix by
+// ballots.  A head at ascending index i with g heads and pb positives before it is group
+// G - 1 - g from the top, with TP = P - pb and FP = (n - i) - TP.
+constexpr int kScanTile = 1024;        // rows per scan tile: 4 sub-chunks of kThreads rows
+constexpr int kTileScanThreads = 1024; // threads of the one block that scans the tile totals
+
+__device__ __forceinline__ float order_key_inv(uint32_t k) {
+  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);  // the -0/+0 class comes back as +0
+}
+
+__device__ __forceinline__ bool group_head(const uint32_t* __restrict__ key, int64_t i) {
+  return i == 0 || key[i] != key[i - 1];
+}
+
+// tile_tot[tile] = (#heads << 32) | #positives of rows [tile * kScanTile, min(n, (tile + 1) * kScanTile))
+__global__ __launch_bounds__(kThreads) void pr_tile_totals_kernel(const uint32_t* __restrict__ key,
+                                                                  const uint8_t* __restrict__ lab, int64_t n,
+                                                                  int64_t ntiles,
+                                                                  unsigned long long* __restrict__ tile_tot) {
+  __shared__ unsigned long long red[kThreads / kWave];
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t b0 = tile * kScanTile;
+    unsigned long long c = 0;
+#pragma unroll
+    for (int j = 0; j < kScanTile / kThreads; ++j) {
+      const int64_t i = b0 + j * kThreads + threadIdx.x;
+      if (i < n) c += ((unsigned long long)group_head(key, i) << 32) | (unsigned long long)(lab[i] != 0);
+    }
+    c = wave_sum(c);
+    __syncthreads();  // the previous tile's read of red
+    if (lane_id() == 0) red[wave_id()] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      unsigned long long t = 0;
+      for (int w = 0; w < kThreads / kWave; ++w) t += red[w];
+      tile_tot[tile] = t;
+    }
+  }
+}
+
+// One block: exclusive scan of the packed tile totals in place, kTileScanThreads per trip with a
+// running carry; tot[0] = G, tot[1] = P (tot[2], the AP sum, was zeroed by the launcher).
+__global__ __launch_bounds__(kTileScanThreads) void pr_tile_scan_kernel(unsigned long long* __restrict__ tile_tot,
+                                                                        int64_t ntiles,
+                                                                        unsigned long long* __restrict__ tot) {
+  __shared__ unsigned long long wsum[kTileScanThreads / kWave];
+  const int t = threadIdx.x, lane = lane_id(), w = wave_id();
+  unsigned long long carry = 0;
+  for (int64_t base = 0; base < ntiles; base += kTileScanThreads) {
+    const int64_t i = base + t;
+    const unsigned long long v = i < ntiles ? tile_tot[i] : 0ull;
+    unsigned long long inc = v;
+#pragma unroll
+    for (int o = 1; o < kWave; o <<= 1) {
+      const unsigned long long u = __shfl_up(inc, o, kWave);
+      if (lane >= o) inc += u;
+    }
+    __syncthreads();  // the previous trip's reads of wsum
+    if (lane == kWave - 1) wsum[w] = inc;
+    __syncthreads();
+    unsigned long long wb = 0, all = 0;
+    for (int k = 0; k < kTileScanThreads / kWave; ++k) {
+      const unsigned long long x = wsum[k];
+      wb += k < w ? x : 0ull;
+      all += x;
+    }
+    if (i < ntiles) tile_tot[i] = carry + wb + inc - v;
+    carry += all;
+  }
+  if (t == 0) {
+    tot[0] = carry >> 32;
+    tot[1] = carry & 0xffffffffull;
+  }
+}
+
+// Every group head writes its (tp, fp[, thr]) into its descending slot (thr may be null).
+__global__ __launch_bounds__(kThreads) void pr_emit_kernel(const uint32_t* __restrict__ key,
+                                                           const uint8_t* __restrict__ lab, int64_t n,
+                                                           int64_t ntiles,
+                                                           const unsigned long long* __restrict__ tile_off,
+                                                           const unsigned long long* __restrict__ tot,
+                                                           uint32_t* __restrict__ tp, uint32_t* __restrict__ fp,
+                                                           float* __restrict__ thr) {
+  __shared__ unsigned long long wcnt[kThreads / kWave];
+  const int lane = lane_id(), w = wave_id();
+  const uint64_t lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+  const int64_t G = (int64_t)tot[0], P = (int64_t)tot[1];
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    unsigned long long run = tile_off[tile];  // (heads, positives) before the sub-chunk
+#pragma unroll
+    for (int j = 0; j < kScanTile / kThreads; ++j) {
+      const int64_t i = tile * kScanTile + j * kThreads + threadIdx.x;
+      const bool valid = i < n;
+      const uint32_t k = valid ? key[i] : 0u;
+      const bool head = valid && group_head(key, i);
+      const bool pos = valid && lab[i] != 0;
+      const uint64_t hb = __ballot(head), pb = __ballot(pos);
+      __syncthreads();  // the previous sub-chunk's reads of wcnt
+      if (lane == 0) wcnt[w] = ((unsigned long long)__popcll(hb) << 32) | (unsigned long long)__popcll(pb);
+      __syncthreads();
+      unsigned long long before = run, all = 0;
+#pragma unroll
+      for (int v = 0; v < kThreads / kWave; ++v) {
+        const unsigned long long x = wcnt[v];
+        before += v < w ? x : 0ull;
+        all += x;
+      }
+      if (head) {
+        const int64_t g_asc = (int64_t)(before >> 32) + __popcll(hb & lt);
+        const int64_t pbef = (int64_t)(before & 0xffffffffull) + __popcll(pb & lt);
+        const int64_t slot = G - 1 - g_asc;
+        const int64_t tpv = P - pbef;
+        tp[slot] = (uint32_t)tpv;
+        fp[slot] = (uint32_t)((n - i) - tpv);
+        if (thr != nullptr) thr[slot] = order_key_inv(k);
+      }
+      run += all;
+    }
+  }
+}
+
+// tot[2] += sum_g rint(dtp[g] * (TP[g] / (TP[g] + FP[g])) * 2^30) over the G emitted groups
+__global__ __launch_bounds__(kThreads) void pr_ap_kernel(const uint32_t* __restrict__ tp,
+                                                         const uint32_t* __restrict__ fp,
+                                                         unsigned long long* __restrict__ tot) {
+  const int64_t G = (int64_t)tot[0];
+  unsigned long long acc = 0;
+  for (int64_t g = (int64_t)blockIdx.x * kThreads + threadIdx.x; g < G; g += (int64_t)gridDim.x * kThreads) {
+    const uint32_t t = tp[g];
+    const uint32_t dtp = t - (g > 0 ? tp[g - 1] : 0u);
+    if (dtp == 0u) continue;
+    const double prec = (double)t / ((double)t + (double)fp[g]);  // t + fp <= n < 2^32: the sum is exact
+    acc += (unsigned long long)__builtin_rint((double)dtp * prec * 1073741824.0);
+  }
+  acc = wave_sum(acc);
+  if (lane_id() == 0 && acc) atomicAdd(tot + 2, acc);
+}
+
+// res = (ap_q, P, N, G) (int64); ap[0] = ap_q / 2^30 / P (NaN without positives)
+__global__ void pr_finalize_kernel(const unsigned long long* __restrict__ tot, int64_t n,
+                                   int64_t* __restrict__ res, double* __restrict__ ap) {
+  const long long G = (long long)tot[0], P = (long long)tot[1], q = (long long)tot[2];
+  res[0] = q;
+  res[1] = P;
+  res[2] = n - P;
+  res[3] = G;
+  ap[0] = P > 0 ? (double)q / 1073741824.0 / (double)P : __builtin_nan("");
+}
+
 }  // namespace
 
 // Workspace layout, every region 256-byte aligned (the u64 counters take 64-bit atomics; an odd n
@@ -410,40 +569,105 @@ size_t auc_radix_workspace_bytes(int64_t n) {
   return off[7];
 }
 
+// The sort of launch_auc_radix and of the precision-recall entry points: (score key, label) of
+// n > 0 rows, stably sorted ascending by (key, label), in the sort regions of a workspace laid out
+// by auc_radix_layout (`off`).  *key / *lab are the arrays that hold the sorted rows.
+static void radix_sort_pairs(const float* scores, const uint8_t* labels, int64_t n, char* p, const size_t off[8],
+                             const uint32_t** key, const uint8_t** lab, hipStream_t stream) {
+  uint32_t* k0 = reinterpret_cast<uint32_t*>(p + off[0]);
+  uint32_t* k1 = reinterpret_cast<uint32_t*>(p + off[1]);
+  uint8_t* l0 = reinterpret_cast<uint8_t*>(p + off[2]);
+  uint8_t* l1 = reinterpret_cast<uint8_t*>(p + off[3]);
+  uint32_t* hist = reinterpret_cast<uint32_t*>(p + off[4]);
+  uint32_t* tot = reinterpret_cast<uint32_t*>(p + off[6]);
+  radix_init_kernel<<<stream_grid(n, kThreads, 4096), kThreads, 0, stream>>>(scores, labels, n, k0, l0);
+  // fewer blocks for small inputs (each owns a contiguous, 256-aligned range)
+  int64_t per_blk = (n + kRadixBlocks - 1) / kRadixBlocks;
+  per_blk = std::max<int64_t>(kThreads, (per_blk + kThreads - 1) / kThreads * kThreads);
+  const int nblk = (int)((n + per_blk - 1) / per_blk);
+  const int shifts[5] = {-1, 0, 8, 16, 24};  // label digit first (least significant), then key bytes
+  for (int ps = 0; ps < 5; ++ps) {
+    radix_hist_kernel<<<nblk, kThreads, 0, stream>>>(k0, l0, n, shifts[ps], per_blk, hist);
+    radix_rowscan_kernel<<<256, 1024, 0, stream>>>(hist, nblk, tot);
+    radix_scatter_kernel<<<nblk, kThreads, 0, stream>>>(k0, l0, n, shifts[ps], per_blk, hist, tot, k1, l1);
+    std::swap(k0, k1);
+    std::swap(l0, l1);
+  }
+  *key = k0;
+  *lab = l0;
+}
+
 void launch_auc_radix(const float* scores, const uint8_t* labels, int64_t n, void* ws, int64_t* res, double* auc,
                       hipStream_t stream) {
   if (reinterpret_cast<uintptr_t>(ws) % 256 != 0) throw std::runtime_error("auc_radix: workspace must be 256-byte aligned");
   size_t off[8];
   auc_radix_layout(n, off);
   char* p = static_cast<char*>(ws);
-  uint32_t* k0 = reinterpret_cast<uint32_t*>(p + off[0]);
-  uint32_t* k1 = reinterpret_cast<uint32_t*>(p + off[1]);
-  uint8_t* l0 = reinterpret_cast<uint8_t*>(p + off[2]);
-  uint8_t* l1 = reinterpret_cast<uint8_t*>(p + off[3]);
-  uint32_t* hist = reinterpret_cast<uint32_t*>(p + off[4]);
   unsigned long long* cnt = reinterpret_cast<unsigned long long*>(p + off[5]);
-  uint32_t* tot = reinterpret_cast<uint32_t*>(p + off[6]);
   if (hipMemsetAsync(cnt, 0, 3 * sizeof(unsigned long long), stream) != hipSuccess)
     throw std::runtime_error("auc_radix: memset failed");
   if (n > 0) {
     if (n > 0xFFFFFFFFll) throw std::runtime_error("auc_radix: at most 2^32 scores");
-    radix_init_kernel<<<stream_grid(n, kThreads, 4096), kThreads, 0, stream>>>(scores, labels, n, k0, l0);
-    // fewer blocks for small inputs (each owns a contiguous, 256-aligned range)
-    int64_t per_blk = (n + kRadixBlocks - 1) / kRadixBlocks;
-    per_blk = std::max<int64_t>(kThreads, (per_blk + kThreads - 1) / kThreads * kThreads);
-    const int nblk = (int)((n + per_blk - 1) / per_blk);
-    const int shifts[5] = {-1, 0, 8, 16, 24};  // label digit first (least significant), then key bytes
-    for (int ps = 0; ps < 5; ++ps) {
-      radix_hist_kernel<<<nblk, kThreads, 0, stream>>>(k0, l0, n, shifts[ps], per_blk, hist);
-      radix_rowscan_kernel<<<256, 1024, 0, stream>>>(hist, nblk, tot);
-      radix_scatter_kernel<<<nblk, kThreads, 0, stream>>>(k0, l0, n, shifts[ps], per_blk, hist, tot, k1, l1);
-      std::swap(k0, k1);
-      std::swap(l0, l1);
-    }
-    auc_sorted_count_kernel<<<stream_grid(n, kThreads * 4, 2048), kThreads, 0, stream>>>(k0, l0, n, cnt);
+    const uint32_t* key;
+    const uint8_t* lab;
+    radix_sort_pairs(scores, labels, n, p, off, &key, &lab, stream);
+    auc_sorted_count_kernel<<<stream_grid(n, kThreads * 4, 2048), kThreads, 0, stream>>>(key, lab, n, cnt);
   }
   auc_sorted_finalize_kernel<<<1, 1, 0, stream>>>(cnt, n, res, auc);
   check_launch("auc_radix");
+}
+
+// Precision-recall workspace: the sort's regions (auc_radix_layout, [0, off[0])) | tile (u64
+// [ceil(n / kScanTile)], the packed tile totals, scanned in place) | tot (u64 [4]: G, P, ap_q) |
+// tp | fp (u32 [n], the AP-only entry's curve).  Offsets in bytes, 256-byte aligned; [5] = total.
+int pr_scan_tile() { return kScanTile; }
+int pr_tile_scan_threads() { return kTileScanThreads; }
+
+void pr_layout(int64_t n, size_t off[6]) {
+  const size_t nn = (size_t)(n > 0 ? n : 0);
+  size_t so[8];
+  auc_radix_layout(n, so);
+  off[0] = so[7];
+  off[1] = align256(off[0] + (nn + kScanTile - 1) / kScanTile * sizeof(unsigned long long));
+  off[2] = align256(off[1] + 4 * sizeof(unsigned long long));
+  off[3] = align256(off[2] + nn * 4);
+  off[4] = align256(off[3] + nn * 4);
+  off[5] = off[4];
+}
+
+size_t pr_workspace_bytes(int64_t n) {
+  size_t off[6];
+  pr_layout(n, off);
+  return off[5];
+}
+
+void launch_pr_curve(const float* scores, const uint8_t* labels, int64_t n, void* ws, uint32_t* tp, uint32_t* fp,
+                     float* thr, int64_t* res, double* ap, hipStream_t stream) {
+  if (n < 0 || n > 0xFFFFFFFFll - 1) throw std::runtime_error("pr_curve: at most 2^32 - 1 scores");
+  if (reinterpret_cast<uintptr_t>(ws) % 256 != 0) throw std::runtime_error("pr_curve: workspace must be 256-byte aligned");
+  size_t so[8], off[6];
+  auc_radix_layout(n, so);
+  pr_layout(n, off);
+  char* p = static_cast<char*>(ws);
+  unsigned long long* tile = reinterpret_cast<unsigned long long*>(p + off[0]);
+  unsigned long long* tot = reinterpret_cast<unsigned long long*>(p + off[1]);
+  if (tp == nullptr) tp = reinterpret_cast<uint32_t*>(p + off[2]);
+  if (fp == nullptr) fp = reinterpret_cast<uint32_t*>(p + off[3]);
+  if (hipMemsetAsync(tot, 0, 4 * sizeof(unsigned long long), stream) != hipSuccess)
+    throw std::runtime_error("pr_curve: memset failed");
+  if (n > 0) {
+    const uint32_t* key;
+    const uint8_t* lab;
+    radix_sort_pairs(scores, labels, n, p, so, &key, &lab, stream);
+    const int64_t ntiles = (n + kScanTile - 1) / kScanTile;
+    const int grid = stream_grid(ntiles, 1, 4096);
+    pr_tile_totals_kernel<<<grid, kThreads, 0, stream>>>(key, lab, n, ntiles, tile);
+    pr_tile_scan_kernel<<<1, kTileScanThreads, 0, stream>>>(tile, ntiles, tot);
+    pr_emit_kernel<<<grid, kThreads, 0, stream>>>(key, lab, n, ntiles, tile, tot, tp, fp, thr);
+    pr_ap_kernel<<<stream_grid(n, kThreads * 4, 2048), kThreads, 0, stream>>>(tp, fp, tot);
+  }
+  pr_finalize_kernel<<<1, 1, 0, stream>>>(tot, n, res, ap);
+  check_launch("pr_curve");
 }
 
 void launch_auc_compact(const float* scores, const uint8_t* labels, int64_t n, float* pos,

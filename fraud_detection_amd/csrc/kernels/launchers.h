@@ -375,6 +375,16 @@ size_t auc_radix_workspace_bytes(int64_t n);
 void auc_radix_layout(int64_t n, size_t off[8]);
 void launch_auc_radix(const float* scores, const uint8_t* labels, int64_t n, void* ws, int64_t* res, double* auc,
                       hipStream_t stream);
+// exact precision-recall curve + average precision on the same sort: group g from the top has
+// thr[g] and the inclusive counts tp[g] / fp[g] (outputs of capacity n; null tp / fp = keep the
+// curve in the workspace, null thr = not written); res = (ap_q, P, N, G), ap = ap_q / 2^30 / P.
+// pr_layout: byte offsets of tile | tot | tp | fp behind the sort's regions, [5] = total.
+int pr_scan_tile();
+int pr_tile_scan_threads();
+size_t pr_workspace_bytes(int64_t n);
+void pr_layout(int64_t n, size_t off[6]);
+void launch_pr_curve(const float* scores, const uint8_t* labels, int64_t n, void* ws, uint32_t* tp, uint32_t* fp,
+                     float* thr, int64_t* res, double* ap, hipStream_t stream);
 void launch_auc_count(const float* scores, const uint8_t* labels, int64_t n, const float* pos,
                       const unsigned long long* counter, int chunk, int nchunks,
                       unsigned long long* out_pairs, hipStream_t stream);

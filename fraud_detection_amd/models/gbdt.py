@@ -90,7 +90,9 @@ class GBDTClassifier:
 
     def fit(self, X, y, comm=None, eval_set=None, verbose: bool = False):
         """``eval_set``: ``[(Xv, yv)]`` (exactly one set, xgboost's list form) evaluated after every
-        round with the constructor's ``eval_metric`` (a name or a list; default "logloss"); with
+        round with the constructor's ``eval_metric`` (a name or a list of "logloss", "error", "auc",
+        "aucpr"; default "logloss"; "aucpr" is sklearn's average precision over tie groups, which
+        xgboost's ``aucpr`` interpolates slightly differently); with
         ``early_stopping_rounds`` the last metric stops the fit and the model keeps trees
         [: best_iteration + 1] (xgboost keeps the tail and never predicts with it).  Without
         ``eval_set`` nothing is evaluated."""
@@ -210,7 +212,8 @@ class GBDTResult:
             margin, y = margin.reshape(-1).contiguous(), y.reshape(-1).contiguous()
         auc = metric_ops.roc_auc(margin, y)
         tn, fp, fn, tp = (int(v) for v in metric_ops.confusion_counts(margin, y, 0.0))
-        return {"auc": auc, "tn": tn, "fp": fp, "fn": fn, "tp": tp, "recall": tp / max(tp + fn, 1),
+        return {"auc": auc, "average_precision": metric_ops.average_precision(margin, y),
+                "tn": tn, "fp": fp, "fn": fn, "tp": tp, "recall": tp / max(tp + fn, 1),
                 "precision": tp / max(tp + fp, 1), "accuracy": (tp + tn) / max(tn + fp + fn + tp, 1)}
 
     def save(self, model_dir: str, feature_names) -> dict:

@@ -75,8 +75,8 @@ class DeviceGBDTCV:
     def __init__(self, cfg: TrainConfig | None = None, params: gb.GBDTParams | None = None, n_folds: int = 5,
                  seed: int = 42, scale_pos_weight: float | str = "auto", eval_metric=None,
                  early_stopping_rounds: int | None = None):
-        """``eval_metric`` (a name or a list of "logloss", "error", "auc"): every fold is evaluated on
-        its own block after each round (ops/gbdt.fit_binned eval_set="hole").  With
+        """``eval_metric`` (a name or a list of "logloss", "error", "auc", "aucpr"): every fold is
+        evaluated on its own block after each round (ops/gbdt.fit_binned eval_set="hole").  With
         ``early_stopping_rounds`` each fold stops by the last metric and keeps its best trees, the
         fold AUCs are those of the kept trees, and the final fit grows round(mean(best_iteration + 1))
         trees instead of ``n_estimators``.  Without either the job is unchanged."""

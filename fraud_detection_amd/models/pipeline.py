@@ -717,7 +717,8 @@ def evaluate(result: PipelineResult, X_test: torch.Tensor, y_test: torch.Tensor,
     auc = metric_ops.roc_auc(logit, y_test)
     cm = metric_ops.confusion_counts(logit, y_test, 0.0)
     tn, fp, fn, tp = (int(v) for v in cm)
-    return {"auc": auc, "tn": tn, "fp": fp, "fn": fn, "tp": tp,
+    return {"auc": auc, "average_precision": metric_ops.average_precision(logit, y_test),
+            "tn": tn, "fp": fp, "fn": fn, "tp": tp,
             "recall": tp / max(tp + fn, 1), "precision": tp / max(tp + fp, 1),
             "accuracy": (tp + tn) / max(tn + fp + fn + tp, 1)}
 

@@ -191,7 +191,7 @@ class _Workspace:
 
 
 # ---- per-round evaluation and early stopping -------------------------------------------------
-EVAL_METRICS = ("logloss", "error", "auc")
+EVAL_METRICS = ("logloss", "error", "auc", "aucpr")
 
 
 @dataclass
@@ -201,8 +201,9 @@ class EvalRecord:
     ``history``: metric name -> one float per round (up to and including the round the fit
     stopped after); ``records``: the exact int64 [rounds, 4] (loss_q, n_err, n_pos, n_rows) behind
     them (logloss = loss_q / 2^30 / n_rows, error = n_err / n_rows) and ``twice_pairs`` the AUC's
-    exact pair counts (auc = twice_pairs / (2 P N)).  ``best_iteration`` is the first round with
-    the best value of the LAST metric, ``best_score`` that value."""
+    exact pair counts (auc = twice_pairs / (2 P N)), ``ap_q`` the average precision's exact integer
+    sums (aucpr = ap_q / 2^30 / P, NaN without positives).  ``best_iteration`` is the first round
+    with the best value of the LAST metric, ``best_score`` that value."""
     history: dict
     best_iteration: int
     best_score: float
@@ -210,6 +211,7 @@ class EvalRecord:
     records: np.ndarray | None = None
     twice_pairs: np.ndarray | None = None
     stopped: bool = False
+    ap_q: np.ndarray | None = None
 
     @property
     def n_rounds(self) -> int:
@@ -243,6 +245,7 @@ class _Eval:
         self.metrics, self.patience, self.T = metrics, patience, T
         self.records = np.zeros((T, 4), np.int64)
         self.twice = np.zeros(T, np.int64)
+        self.apq = np.zeros(T, np.int64)
         self.done = 0          # records pushed
         self.best = 0
         self.stop_at = None    # the round the rule fired after
@@ -251,15 +254,22 @@ class _Eval:
     def want_auc(self) -> bool:
         return "auc" in self.metrics
 
+    @property
+    def want_aucpr(self) -> bool:
+        return "aucpr" in self.metrics
+
     def key(self, t: int) -> int:
         last = self.metrics[-1]
+        if last == "aucpr":  # P is the same in every round: -ap_q orders the rounds as -AP does
+            return int(-self.apq[t])
         return int(-self.twice[t]) if last == "auc" else int(self.records[t, 0 if last == "logloss" else 1])
 
-    def push(self, rec, twice=0) -> bool:
+    def push(self, rec, twice=0, ap_q=0) -> bool:
         """Record of round ``self.done``; True when the fit stops after that round."""
         t = self.done
         self.records[t] = rec
         self.twice[t] = twice
+        self.apq[t] = ap_q
         self.done = t + 1
         if t == 0 or self.key(t) < self.key(self.best):
             self.best = t
@@ -275,7 +285,7 @@ class _Eval:
 
     def result(self) -> EvalRecord:
         k = self.done
-        rec, tw = self.records[:k].copy(), self.twice[:k].copy()
+        rec, tw, aq = self.records[:k].copy(), self.twice[:k].copy(), self.apq[:k].copy()
         rows = np.maximum(rec[:, 3], 1).astype(np.float64)
         P = rec[:, 2].astype(np.float64)
         N = rec[:, 3].astype(np.float64) - P
@@ -285,6 +295,9 @@ class _Eval:
                 v = rec[:, 0].astype(np.float64) / R.LOSS_SCALE / rows
             elif name == "error":
                 v = rec[:, 1].astype(np.float64) / rows
+            elif name == "aucpr":
+                with np.errstate(all="ignore"):
+                    v = np.where(P > 0, aq.astype(np.float64) / R.LOSS_SCALE / P, np.nan)
             else:
                 with np.errstate(all="ignore"):
                     v = np.where((P > 0) & (N > 0), tw.astype(np.float64) / (2.0 * P * N), np.nan)
@@ -292,7 +305,7 @@ class _Eval:
         best_score = hist[self.metrics[-1]][self.best] if k else float("nan")
         return EvalRecord(history=hist, best_iteration=int(self.best), best_score=float(best_score),
                           metrics=tuple(self.metrics), records=rec, twice_pairs=tw if self.want_auc else None,
-                          stopped=self.stop_at is not None)
+                          stopped=self.stop_at is not None, ap_q=aq if self.want_aucpr else None)
 
 
 def _eval_request(eval_set, eval_metric, early_stopping_rounds, hole_len, checkpoint, dist, T):
@@ -311,6 +324,9 @@ def _eval_request(eval_set, eval_metric, early_stopping_rounds, hole_len, checkp
     if "auc" in metrics and dist:
         raise NotImplementedError("eval_metric 'auc' is not supported under data-parallel training "
                                   "(pair counts do not add across ranks)")
+    if "aucpr" in metrics and dist:
+        raise NotImplementedError("eval_metric 'aucpr' is not supported under data-parallel training "
+                                  "(the tie-group sums do not add across ranks)")
     if early_stopping_rounds is not None and int(early_stopping_rounds) < 1:
         raise ValueError("early_stopping_rounds must be >= 1")
     patience = None if early_stopping_rounds is None else int(early_stopping_rounds)
@@ -385,9 +401,12 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
     ``eval_set``: ``(Xv, yv)`` -- standardized float32 rows (binned here with the fit's cuts) or
     already-binned u8 [m, 32] rows, with uint8 labels -- or the string ``"hole"``: the hole's rows,
     whose margins every round's walk keeps current anyway.  Exactly one eval set.  After every round
-    the metrics of ``eval_metric`` ("logloss", "error", "auc") are taken on it as exact integers
-    (gbdt.hip gbdt_eval_kernel; EvalRecord).  Without ``early_stopping_rounds`` this changes nothing
-    about the trees.  With it, the LAST metric drives the stop rule (as in xgboost): a round improves
+    the metrics of ``eval_metric`` ("logloss", "error", "auc", "aucpr") are taken on it as exact
+    integers (gbdt.hip gbdt_eval_kernel; EvalRecord).  "aucpr" is sklearn's average precision over
+    the tie groups of the margins (auc.hip, ops/metrics.average_precision_device); xgboost's
+    ``aucpr`` interpolates the curve slightly differently, so its values differ a little.  Without
+    ``early_stopping_rounds`` this changes nothing about the trees.
+    With it, the LAST metric drives the stop rule (as in xgboost): a round improves
     when its integer sum is strictly better than the best so far, and the fit stops after the first
     round t with t - best >= early_stopping_rounds.  The host waits for round t - patience's record
     before it enqueues round t, so at most ``early_stopping_rounds`` rounds are in flight and the
@@ -479,7 +498,8 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
                 rec = R.eval_record(m_ev, y_ev)
                 if comm is not None and comm.world_size > 1:
                     rec = comm.all_reduce(torch.from_numpy(rec)).numpy()
-                if ev.push(rec, R.twice_pairs(m_ev, y_ev) if ev.want_auc else 0):
+                if ev.push(rec, R.twice_pairs(m_ev, y_ev) if ev.want_auc else 0,
+                           R.ap_q(m_ev, y_ev) if ev.want_aucpr else 0):
                     break
         if ev is not None and ev.n_keep < T:  # early stop: keep [: best + 1], margins of the kept trees
             k = ev.n_keep
@@ -589,6 +609,8 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
     fuse_margin = os.environ.get("FDX_GBDT_FUSE_MARGIN", "0") == "1" and not graphable and ev is None
     graph = None
     if ev is not None:
+        from . import metrics as metric_ops
+
         # device history, zeroed once (the kernel adds into a round's row); pinned host mirror the
         # round's record is copied into on the fit's stream, with one event per round
         ev_hist = torch.zeros((T, 4), dtype=torch.int64, device=dev)
@@ -607,6 +629,10 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
             ev_tw = torch.zeros(T, dtype=torch.int64, device=dev)
             tw_host = torch.zeros(T, dtype=torch.int64).pin_memory()
             ev_pos = int(y_ev.sum(dtype=torch.int64).item())  # the positive count, read once
+        if ev.want_aucpr:
+            ev_ap = torch.zeros(T, dtype=torch.int64, device=dev)
+            ap_host = torch.zeros(T, dtype=torch.int64).pin_memory()
+            ap_ws = metric_ops.pr_workspace(int(m_ev.shape[0]), dev)  # the sort's scratch, once per fit
 
         def eval_round(t):
             st = stream_of(bins)
@@ -619,18 +645,21 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
                 comm.all_reduce_(ev_hist[t])
             ev_host[t].copy_(ev_hist[t], non_blocking=True)
             if ev.want_auc:
-                from . import metrics as metric_ops
-
                 _, twice = metric_ops.auc_known_positives(m_ev, y_ev, ev_pos)
                 ev_tw[t].copy_(twice)
                 tw_host[t:t + 1].copy_(ev_tw[t:t + 1], non_blocking=True)
+            if ev.want_aucpr:
+                _, ap_res = metric_ops.average_precision_device(m_ev, y_ev, ws=ap_ws)
+                ev_ap[t].copy_(ap_res[0])
+                ap_host[t:t + 1].copy_(ev_ap[t:t + 1], non_blocking=True)
             ev_done[t] = torch.cuda.Event()
             ev_done[t].record()
 
         def eval_take(s):
             """Wait for round s's record and apply the stop rule to it."""
             ev_done[s].synchronize()
-            return ev.push(ev_host[s].numpy(), int(tw_host[s]) if ev.want_auc else 0)
+            return ev.push(ev_host[s].numpy(), int(tw_host[s]) if ev.want_auc else 0,
+                           int(ap_host[s]) if ev.want_aucpr else 0)
 
     rounds_run = t0
     for t in range(t0, T):

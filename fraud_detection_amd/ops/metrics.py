@@ -1,4 +1,5 @@
-"""K10 exact ROC-AUC and confusion counts."""
+"""K10 exact ROC-AUC, confusion counts, and the exact precision-recall curve / average precision
+with its operating points."""
 from __future__ import annotations
 
 import numpy as np
@@ -134,11 +135,124 @@ def confusion_counts(scores: torch.Tensor, labels: torch.Tensor, threshold: floa
     return out.cpu().numpy()
 
 
+# ---- exact precision-recall curve, average precision and operating points ---------------------
+def pr_workspace(n: int, dev) -> torch.Tensor:
+    """Workspace of the precision-recall kernels for up to ``n`` scores: a per-round caller (the
+    GBDT's aucpr) allocates it once and passes it as ``ws``."""
+    return torch.empty(int(native().pr_workspace_bytes(int(n))), dtype=torch.uint8, device=dev)
+
+
+def _pr_ws(n: int, dev, ws):
+    if ws is None:
+        return _radix_ws(dev, int(native().pr_workspace_bytes(n)))
+    if ws.dtype != torch.uint8 or ws.device != dev or ws.numel() < int(native().pr_workspace_bytes(n)):
+        raise ValueError("ws must be a uint8 tensor of at least pr_workspace_bytes(n) on the scores' device")
+    return ws
+
+
+def average_precision_device(scores: torch.Tensor, labels: torch.Tensor, ws: torch.Tensor | None = None):
+    """Exact average precision on device with no host synchronisation: the radix sort of
+    (score key, label), a device-wide scan of (tie-group heads, positives), the tie-group walk and
+    one integer reduction (csrc/kernels/auc.hip).  Returns (ap float64 0-dim device tensor,
+    int64 [4] device tensor = (ap_q, P, N, G)) with ap = ap_q / 2^30 / P (NaN without positives),
+    ap_q = sum over tie groups of rint(dtp * precision * 2^30): sklearn's average_precision_score
+    within 2^-31, as an order-independent integer (ops/reference.py average_precision_q).  ``ws``:
+    an optional caller-owned workspace (pr_workspace).  NaN scores are not supported, as in the AUC
+    paths; +-inf are ordinary scores."""
+    _check(scores, labels)
+    n = scores.shape[0]
+    dev = scores.device
+    if n == 0:  # nothing to launch
+        return (torch.full((), float("nan"), dtype=torch.float64, device=dev),
+                torch.zeros(4, dtype=torch.int64, device=dev))
+    m = native()
+    ws = _pr_ws(n, dev, ws)
+    res = torch.empty(4, dtype=torch.int64, device=dev)
+    ap = torch.empty((), dtype=torch.float64, device=dev)
+    m.pr_curve(ptr(scores), ptr(labels), n, ptr(ws), 0, 0, 0, ptr(res), ptr(ap), stream_of(scores))
+    return ap, res
+
+
+def average_precision(scores: torch.Tensor, labels: torch.Tensor) -> float:
+    """Average precision (ties grouped), equal to sklearn.metrics.average_precision_score within
+    2^-31; NaN without positives.  GPU tensors take the kernels, CPU tensors the numpy oracle.  NaN
+    scores are not supported."""
+    _check(scores, labels)
+    if not scores.is_cuda:
+        return ref.average_precision(scores.numpy(), labels.numpy())
+    ap, _ = average_precision_device(scores, labels)
+    return float(ap.item())
+
+
+def pr_curve(scores: torch.Tensor, labels: torch.Tensor):
+    """Exact precision-recall curve: (thr float32 [G], tp int64 [G], fp int64 [G]) numpy arrays
+    over the G tie groups, descending threshold, tp / fp = positives / negatives with
+    score >= thr[g] (precision_recall(...) turns them into sklearn's precision_recall_curve without
+    its appended (1, 0) point).  On a GPU: the kernels of average_precision_device, one read-back
+    of G and one of the three slices.  NaN scores are not supported; -0.0 and +0.0 are one group,
+    reported as +0.0."""
+    _check(scores, labels)
+    n = scores.shape[0]
+    if not scores.is_cuda or n == 0:
+        return ref.pr_curve(scores.cpu().numpy(), labels.cpu().numpy())
+    m = native()
+    dev = scores.device
+    ws = _pr_ws(n, dev, None)
+    thr = torch.empty(n, dtype=torch.float32, device=dev)
+    tp = torch.empty(n, dtype=torch.int32, device=dev)  # u32 counts
+    fp = torch.empty(n, dtype=torch.int32, device=dev)
+    res = torch.empty(4, dtype=torch.int64, device=dev)
+    ap = torch.empty((), dtype=torch.float64, device=dev)
+    m.pr_curve(ptr(scores), ptr(labels), n, ptr(ws), ptr(tp), ptr(fp), ptr(thr), ptr(res), ptr(ap), stream_of(scores))
+    G = int(res[3].item())
+    cnt = torch.stack([tp[:G], fp[:G]]).cpu().numpy().view(np.uint32).astype(np.int64)
+    return thr[:G].cpu().numpy(), cnt[0], cnt[1]
+
+
+def precision_recall(thr, tp, fp):
+    """(precision, recall) float64 of a curve: tp / (tp + fp) and tp / P (NaN without positives)."""
+    tp = np.asarray(tp, dtype=np.float64)
+    fp = np.asarray(fp, dtype=np.float64)
+    P = tp[-1] if tp.shape[0] else 0.0
+    with np.errstate(all="ignore"):
+        return tp / (tp + fp), (tp / P if P > 0 else np.full(tp.shape, np.nan))
+
+
+def operating_point(thr, tp, fp, *, min_precision: float | None = None, min_recall: float | None = None,
+                    max_alerts: int | None = None) -> dict:
+    """The threshold of a curve (pr_curve / pr_curve_hist) that meets exactly one criterion, with
+    prediction = ``score >= threshold`` (confusion_counts predicts with ``>``):
+
+    ``min_precision``: the lowest threshold whose precision is >= the target (maximum recall);
+    ``min_recall``: the highest threshold whose recall is >= the target;
+    ``max_alerts``: the lowest threshold with tp + fp <= the budget.
+
+    Returns threshold, tp, fp, precision, recall, alerts.  ValueError when no threshold qualifies
+    or when none or several criteria are given."""
+    given = [c is not None for c in (min_precision, min_recall, max_alerts)]
+    if sum(given) != 1:
+        raise ValueError("exactly one of min_precision, min_recall, max_alerts must be given")
+    thr, tp, fp = np.asarray(thr), np.asarray(tp, dtype=np.int64), np.asarray(fp, dtype=np.int64)
+    precision, recall = precision_recall(thr, tp, fp)
+    if min_precision is not None:
+        ok = np.flatnonzero(precision >= float(min_precision))
+        pick = ok[-1] if ok.size else None
+    elif min_recall is not None:
+        ok = np.flatnonzero(recall >= float(min_recall))
+        pick = ok[0] if ok.size else None
+    else:
+        ok = np.flatnonzero(tp + fp <= int(max_alerts))
+        pick = ok[-1] if ok.size else None
+    if pick is None:
+        raise ValueError("no threshold of the curve meets the criterion")
+    g = int(pick)
+    return {"threshold": float(thr[g]), "tp": int(tp[g]), "fp": int(fp[g]), "precision": float(precision[g]),
+            "recall": float(recall[g]), "alerts": int(tp[g] + fp[g])}
+
+
 # ---- histogram AUC (K10 `auc_hist`): mergeable across ranks by summing histograms ------------
 def _order_key_np(scores: np.ndarray) -> np.ndarray:
-    b = np.ascontiguousarray(scores, dtype=np.float32).view(np.uint32)
-    b = np.where(b == np.uint32(0x80000000), np.uint32(0), b)  # -0 == +0
-    return np.where(b & np.uint32(0x80000000), ~b, b | np.uint32(0x80000000)).astype(np.uint32)
+    return ref.order_key(scores)  # -0 == +0
 
 
 def score_histogram(scores: torch.Tensor, labels: torch.Tensor, bits: int = 20) -> torch.Tensor:
@@ -193,3 +307,31 @@ def roc_curve_hist(scores: torch.Tensor, labels: torch.Tensor, bits: int = 16, c
     P, N = max(tp[-1], 1), max(fp[-1], 1)
     keep = np.r_[True, (np.diff(tp) + np.diff(fp)) > 0]
     return np.r_[0.0, fp[keep] / N], np.r_[0.0, tp[keep] / P]
+
+
+def pr_curve_hist(scores: torch.Tensor, labels: torch.Tensor, bits: int = 16, comm=None):
+    """(thr, tp, fp) as pr_curve, from score histograms with every non-empty bin as one tie group
+    -- the data-parallel form: with ``comm`` the histograms of all ranks are summed (one fixed-size
+    all-reduce) instead of gathering every score.  thr[g] is the bin's lower edge, the smallest
+    score the bin can hold (so ``score >= thr[g]`` selects the bin and everything above it; -inf
+    for the bin of -inf).  When all scores in a bin are equal, tp / fp equal the exact curve's, and
+    so does thr for non-negative scores whose low 32 - bits mantissa bits are zero."""
+    hist = score_histogram(scores, labels, bits)
+    if comm is not None and comm.world_size > 1:
+        hist = comm.all_reduce_(hist.contiguous())
+    h = hist.cpu().numpy().astype(np.int64)
+    nz = np.flatnonzero(h[0] + h[1])[::-1]  # non-empty bins, descending
+    tp, fp = np.cumsum(h[1][nz]), np.cumsum(h[0][nz])
+    with np.errstate(invalid="ignore"):
+        thr = ref.order_key_inv(nz.astype(np.uint32) << np.uint32(32 - bits))
+        thr = np.where(np.isnan(thr), np.float32(-np.inf), thr).astype(np.float32)
+    return thr, tp.astype(np.int64), fp.astype(np.int64)
+
+
+def average_precision_hist(scores: torch.Tensor, labels: torch.Tensor, bits: int = 16, comm=None) -> float:
+    """Average precision of pr_curve_hist's curve (scores in one bin count as ties), by the exact
+    curve's integer formula; NaN without positives.  The data-parallel answer, as roc_auc_hist is
+    for the AUC."""
+    _, tp, fp = pr_curve_hist(scores, labels, bits, comm)
+    P = int(tp[-1]) if tp.shape[0] else 0
+    return ref.ap_q_from_curve(tp, fp) / ref.AP_SCALE / P if P else float("nan")

@@ -486,6 +486,72 @@ def roc_auc(scores: np.ndarray, labels: np.ndarray) -> float:
     return float((ranks[y].sum() - P * (P + 1) / 2.0) / (P * N))
 
 
+def order_key(scores: np.ndarray) -> np.ndarray:
+    """Order-preserving uint32 key of float32 scores (auc.hip order_key): a larger score has a
+    larger key, -0.0 and +0.0 share one."""
+    b = np.ascontiguousarray(scores, dtype=np.float32).ravel().view(np.uint32)
+    b = np.where(b == np.uint32(0x80000000), np.uint32(0), b)
+    return np.where(b & np.uint32(0x80000000), ~b, b | np.uint32(0x80000000)).astype(np.uint32)
+
+
+def order_key_inv(key: np.ndarray) -> np.ndarray:
+    """The float32 score of a key; the -0.0 / +0.0 class comes back as +0.0."""
+    k = np.ascontiguousarray(key, dtype=np.uint32)
+    return np.where(k & np.uint32(0x80000000), k & np.uint32(0x7FFFFFFF), ~k).astype(np.uint32).view(np.float32)
+
+
+AP_SCALE = float(2 ** 30)  # fixed point of one tie group's average-precision term
+
+
+def pr_curve(scores: np.ndarray, labels: np.ndarray):
+    """(thr float32 [G], tp int64 [G], fp int64 [G]) over the G tie groups of the scores (float32;
+    -0.0 == +0.0), descending: tp / fp are the counts of positives / negatives with score >= thr[g].
+    precision = tp / (tp + fp), recall = tp / tp[-1] is sklearn.metrics.precision_recall_curve
+    without its appended (1, 0) point and in descending-threshold order.  NaN scores are not
+    supported (as in roc_auc); +-inf are ordinary scores."""
+    key = order_key(scores)
+    y = np.asarray(labels).ravel() != 0
+    if key.shape[0] == 0:
+        return np.zeros(0, np.float32), np.zeros(0, np.int64), np.zeros(0, np.int64)
+    order = np.argsort(key, kind="stable")[::-1]
+    ks, ys = key[order], y[order]
+    last = np.flatnonzero(np.r_[ks[1:] != ks[:-1], True])  # the last row of every group
+    tp = np.cumsum(ys, dtype=np.int64)[last]
+    fp = (last.astype(np.int64) + 1) - tp
+    return order_key_inv(ks[last]), tp, fp
+
+
+def average_precision_q(scores: np.ndarray, labels: np.ndarray):
+    """(ap_q, P, N): ap_q = sum_g rint(dtp[g] * (tp[g] / (tp[g] + fp[g])) * 2^30) over the tie
+    groups of pr_curve, dtp[g] = tp[g] - tp[g-1] -- an exact, order-independent integer (every term
+    is one correctly rounded fp64 division and product, the sum is int64) with
+    |ap_q / 2^30 / P - average_precision_score| <= 2^-31 (each of the <= P non-zero terms is off by
+    at most 0.5).  The oracle of auc.hip's pr_ap_kernel."""
+    _, tp, fp = pr_curve(scores, labels)
+    n = int(np.asarray(labels).size)
+    if tp.shape[0] == 0:
+        return 0, 0, n
+    P = int(tp[-1])
+    return ap_q_from_curve(tp, fp), P, n - P
+
+
+def ap_q_from_curve(tp: np.ndarray, fp: np.ndarray) -> int:
+    """sum_g rint(dtp[g] * (tp[g] / (tp[g] + fp[g])) * 2^30) of a curve's cumulative counts."""
+    tp = np.asarray(tp, dtype=np.int64)
+    fp = np.asarray(fp, dtype=np.int64)
+    if tp.shape[0] == 0:
+        return 0
+    dtp = np.diff(tp, prepend=np.int64(0))
+    term = np.rint(dtp.astype(np.float64) * (tp.astype(np.float64) / (tp + fp).astype(np.float64)) * AP_SCALE)
+    return int(term.astype(np.int64).sum())
+
+
+def average_precision(scores: np.ndarray, labels: np.ndarray) -> float:
+    """ap_q / 2^30 / P (== sklearn.metrics.average_precision_score within 2^-31); NaN without positives."""
+    q, P, _ = average_precision_q(scores, labels)
+    return q / AP_SCALE / P if P else float("nan")
+
+
 def confusion(scores, labels, thr: float):
     s = np.asarray(scores)
     y = np.asarray(labels).astype(bool)

@@ -209,6 +209,14 @@ def twice_pairs(margin: np.ndarray, y: np.ndarray) -> int:
     return int(np.searchsorted(neg, sp, side="left").sum() + np.searchsorted(neg, sp, side="right").sum())
 
 
+def ap_q(margin: np.ndarray, y: np.ndarray) -> int:
+    """The average precision of fp32 margins as an exact integer: sum over tie groups (descending)
+    of rint(dtp * precision * 2^30); AP = ap_q / 2^30 / P (ops/reference.py average_precision_q)."""
+    from .reference import average_precision_q
+
+    return average_precision_q(np.asarray(margin, dtype=np.float32).ravel(), np.asarray(y).ravel())[0]
+
+
 def predict_margin(X: np.ndarray, feat: np.ndarray, thr: np.ndarray, leaf: np.ndarray, depth: int,
                    base_margin: float = 0.0) -> np.ndarray:
     """X [n, d] float32; feat/thr [T, ni]; leaf [T, nl].  float32 margins (sum in tree order)."""

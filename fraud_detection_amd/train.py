@@ -400,7 +400,7 @@ def main(argv=None):
     ap.add_argument("--split", default=None, choices=["auto", "sklearn", "device"],
                     help="sklearn: reference-identical split; device: K3 kernel (default auto: device >= 2M rows on GPU)")
     ap.add_argument("--gbdt-eval-metric", default=None,
-                    help="comma-separated logloss,error,auc: per-round metrics of every CV fold on its own rows "
+                    help="comma-separated logloss,error,auc,aucpr: per-round metrics of every CV fold on its own rows "
                          "(device GBDT CV job); the last one drives early stopping")
     ap.add_argument("--gbdt-early-stopping", type=int, default=None, metavar="N",
                     help="stop a fold after N rounds without improvement; the final fit grows "
