@@ -61,7 +61,7 @@ __device__ __forceinline__ bool is_built(int node, const int64_t* gcnt) {
 
 // ---- quantisation ----------------------------------------------------------------------------
 // 8 lanes per row, 4 features per lane: the 8 lanes write one 32-byte binned row.
-//  * VEC (rows 16-byte aligned, ld % 4 == 0 -- the pipeline's [n, 32] fp32 rows): each lane reads
+//  * VEC (rows 16-byte aligned, ld % 4 == 0, ld >= 32 -- the pipeline's [n, 32] fp32 rows): each lane reads
 //    its 4 features with ONE 16-byte load, so a row is one coalesced 128-byte read (the scalar
 //    form issued 4 loads per lane);
 //  * the upper-bound search is branchless over the 256 cut slots (cuts past nbins are +inf):
@@ -703,7 +703,10 @@ __global__ __launch_bounds__(kHistThreads) void gbdt_split_kernel(
     const long long Gq = __shfl(eg, 63, kWave), Hq = __shfl(eh, 63, kWave);
     const long long pg = eg - g[3], ph = eh - h[3];  // exclusive prefix of this lane
     const double G = (double)Gq * ginv, Hs = (double)Hq * hinv;
-    const double root = G * G / (Hs + lambda);
+    // a term G^2 / (H + lambda) whose denominator is <= 0 counts as 0 (lambda = 0 with an empty or
+    // zero-Hessian side: 0/0 or G^2/0 otherwise) -- the oracle's rule, reference_gbdt.py
+    const double dn = Hs + lambda;
+    const double root = dn > 0.0 ? G * G / dn : 0.0;
     const int nb = nbins[f];
     double best = -1.0e300;
     int bb = 0x7fffffff;
@@ -715,7 +718,8 @@ __global__ __launch_bounds__(kHistThreads) void gbdt_split_kernel(
       const double GL = (double)GLq * ginv, HL = (double)HLq * hinv;
       const double GR = (double)(Gq - GLq) * ginv, HR = (double)(Hq - HLq) * hinv;
       if (b < nb - 1 && HL >= min_child_weight && HR >= min_child_weight) {
-        const double gain = (GL * GL / (HL + lambda) + GR * GR / (HR + lambda)) - root;
+        const double dl = HL + lambda, dr = HR + lambda;
+        const double gain = ((dl > 0.0 ? GL * GL / dl : 0.0) + (dr > 0.0 ? GR * GR / dr : 0.0)) - root;
         if (gain > best) { best = gain; bb = b; bgl = GLq; bhl = HLq; }
       }
     }
@@ -1245,7 +1249,9 @@ __global__ __launch_bounds__(kPredThreads) void gbdt_predict_kernel(
 void launch_gbdt_bin(const float* X, int64_t n, int ld, int d, const float* cuts, const int* nbins,
                      uint8_t* bins, hipStream_t stream) {
   if (d > kGBMaxFeat) throw std::runtime_error("gbdt: at most 30 features");
-  const bool vec = (ld % 4) == 0 && (reinterpret_cast<uintptr_t>(X) % 16) == 0 && d <= 32;
+  // VEC loads float4 columns 0..31 of every row whatever d is, so a row must own 32 floats (the
+  // pipeline's [n, 32] rows): with a narrower ld the last rows' loads would run past the table
+  const bool vec = ld >= 32 && (ld % 4) == 0 && (reinterpret_cast<uintptr_t>(X) % 16) == 0;
   if (vec) {
     static const int cap = resident_cap(gbdt_bin_kernel<true>, 256);
     gbdt_bin_kernel<true><<<capped_grid(n, 256 / 8, cap), 256, 0, stream>>>(X, n, ld, d, cuts, nbins, bins);

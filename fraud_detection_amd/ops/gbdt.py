@@ -48,6 +48,12 @@ class GBDTParams:
             raise ValueError("base_score must be in (0, 1)")
         if self.n_estimators < 0 or self.learning_rate <= 0:
             raise ValueError("bad n_estimators / learning_rate")
+        for name in ("reg_lambda", "min_child_weight", "gamma"):
+            v = float(getattr(self, name))
+            if not np.isfinite(v) or v < 0.0:
+                raise ValueError(f"{name} must be finite and >= 0")
+        if not np.isfinite(float(self.scale_pos_weight)) or self.scale_pos_weight <= 0:
+            raise ValueError("scale_pos_weight must be finite and > 0")
         return self
 
 

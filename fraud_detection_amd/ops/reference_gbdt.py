@@ -9,7 +9,14 @@ same tie rules, so a device fit given the same quantised gradients builds bit-id
   valid when HL, HR >= min_child_weight; argmax over (feature, bin), ties -> lowest feature,
   then lowest bin; split iff gain > 1e-6 and not gain < gamma (xgboost kRtEps / pruner);
 * complete heap trees of depth D; a non-split node passes every row to its left child;
-* leaf = float32(eta * (-G/(H+l))) (0 when H < min_child_weight or H <= 0).
+* leaf = float32(eta * (-G/(H+l))) (0 when H < min_child_weight or H <= 0);
+* a gain term G^2/(H+l) whose denominator H+l is <= 0 counts as 0 -- the node's own term and both
+  child terms alike.  Only reg_lambda = 0 reaches it (an empty side, or rows whose quantised
+  Hessian is 0): the term would be 0/0 or G^2/0, and a NaN or +inf gain decides nothing.  Where
+  every denominator is positive -- every fit with reg_lambda > 0 -- no bit changes.  xgboost's
+  CalcGain zeroes the term on H <= 0 whatever lambda is; that would change finite gains at
+  min_child_weight = 0 (an empty child contributes 0^2/l = 0 either way, but a child with H = 0,
+  G != 0 contributes G^2/l here), so it is deliberately not adopted.
 
 xgboost itself is not installed in this image, so parity with xgboost is "unpinned"; the
 semantics above follow xgboost's hist updater (train_model.py:69-80 uses XGBClassifier).
@@ -117,13 +124,14 @@ def best_split(H: np.ndarray, nbins: np.ndarray, ginv: float, hinv: float, lam: 
     chs = np.cumsum(H[:, :, 1], axis=1)
     Gq, Hq = int(cg[0, -1]), int(chs[0, -1])
     G, Hs = float(Gq) * ginv, float(Hq) * hinv
-    root = G * G / (Hs + lam)
+    root = G * G / (Hs + lam) if Hs + lam > 0.0 else 0.0
     GL = cg.astype(np.float64) * ginv
     HL = chs.astype(np.float64) * hinv
     GR = (Gq - cg).astype(np.float64) * ginv
     HR = (Hq - chs).astype(np.float64) * hinv
-    with np.errstate(all="ignore"):
-        gain = (GL * GL / (HL + lam) + GR * GR / (HR + lam)) - root
+    dl, dr = HL + lam, HR + lam
+    with np.errstate(all="ignore"):  # a term with a denominator <= 0 counts as 0 (module docstring)
+        gain = (np.where(dl > 0.0, GL * GL / dl, 0.0) + np.where(dr > 0.0, GR * GR / dr, 0.0)) - root
     b = np.arange(MAX_BIN)[None, :]
     valid = (b < (nbins[:d, None] - 1)) & (HL >= mcw) & (HR >= mcw)
     gain = np.where(valid, gain, -np.inf)
@@ -160,7 +168,7 @@ def build_tree(bins: np.ndarray, q: np.ndarray, cuts: np.ndarray, nbins: np.ndar
             g_, f, b, GLq, HLq, Gq, Hq = best_split(Hl[k], nbins, ginv, hinv, lam, mcw)
             if hid == 0:
                 ng[0], nh[0] = Gq, Hq
-            split = np.isfinite(g_) and g_ > 1e-6 and not (g_ < gamma)
+            split = accepts_split(g_, gamma)
             lc, rc = 2 * hid + 1, 2 * hid + 2
             if split:
                 feat[hid], binv[hid], thr[hid], gain[hid] = f, b, cuts[f, b], g_
@@ -170,12 +178,24 @@ def build_tree(bins: np.ndarray, q: np.ndarray, cuts: np.ndarray, nbins: np.ndar
             else:
                 ng[lc], nh[lc], ng[rc], nh[rc] = Gq, Hq, 0, 0
         node = 2 * node + right.astype(np.int64)
+    return TreeArrays(feat, binv, thr, gain, leaf_values(ng, nh, depth, ginv, hinv, lam, mcw, eta)), node
+
+
+def accepts_split(gain: float, gamma: float) -> bool:
+    """The split rule on a node's best gain: gain > 1e-6 and not gain < gamma."""
+    return bool(np.isfinite(gain) and gain > 1e-6 and not (gain < gamma))
+
+
+def leaf_values(ng: np.ndarray, nh: np.ndarray, depth: int, ginv: float, hinv: float, lam: float, mcw: float,
+                eta: float) -> np.ndarray:
+    """float32 [2^depth] leaf values from the heap's int64 node sums ng / nh (leaves at 2^depth - 1 ..)."""
+    ni, nl = (1 << depth) - 1, 1 << depth
     leaf = np.zeros(nl, np.float32)
     for i in range(nl):
         G, H = float(ng[ni + i]) * ginv, float(nh[ni + i]) * hinv
         w = 0.0 if (H < mcw or H <= 0.0) else -G / (H + lam)
         leaf[i] = np.float32(eta * w)
-    return TreeArrays(feat, binv, thr, gain, leaf), node
+    return leaf
 
 
 LOSS_CAP = 36.841361487904734  # -ln(1e-16): xgboost clamps p to [eps, 1 - eps], eps = 1e-16

@@ -211,3 +211,79 @@ def test_fit_binned_hole_equals_explicit_copy_cpu():
     assert torch.equal(m_h[keep], m_c)
     ref = gb.R.predict_margin_bins(bins[1000:2500].numpy(), ens_c.feat, ens_c.bin, ens_c.leaf, 3, ens_c.base_margin)
     np.testing.assert_array_equal(m_h[1000:2500].numpy(), ref)
+
+
+@pytest.mark.parametrize("mcw", [0.0, 1.0])
+def test_reg_lambda_zero_fit_does_not_raise(mcw):
+    """40 rows at depth 5 leave pass-through nodes whose right child is empty (H = 0): with
+    reg_lambda = 0 its own gain term is 0/0.  The term counts as 0 (reference_gbdt's header), so the
+    fit runs, every gain is finite and the training margins still equal the inference walk."""
+    X, y = _data(40, 4, seed=3)
+    Xs, ys = torch.from_numpy(X), torch.from_numpy(y)
+    p = gb.GBDTParams(n_estimators=3, max_depth=5, reg_lambda=0.0, min_child_weight=mcw)
+    ens, margin = gb.fit(Xs, ys, p, return_margin=True)
+    assert (ens.feat[:, 15:] == -1).any()  # pass-through nodes: the empty-child case did occur
+    assert np.all(np.isfinite(ens.gain)) and np.all(np.isfinite(ens.leaf))
+    assert np.all(ens.gain[ens.feat >= 0] > 1e-6) and np.all(ens.gain[ens.feat < 0] == 0.0)
+    assert np.array_equal(margin.numpy(), gb.predict_margin(Xs, ens).numpy())
+
+
+def test_best_split_zero_denominator_terms_count_as_zero():
+    """reg_lambda = 0: a bin range with h = 0, g != 0 would score G^2/0 = +inf and an empty node
+    0/0 = NaN; both terms count as 0, so the finite candidate wins and nothing raises."""
+    H = np.zeros((1, 256, 2), np.int64)
+    H[0, 0], H[0, 1], H[0, 2] = (5, 0), (-3, 4), (4, 4)
+    nb = np.array([3], np.int32)
+    # totals (6, 8): root 36/8 = 4.5; b = 0: 0 + 1/8 - 4.5; b = 1: 4/4 + 16/4 - 4.5 = 0.5
+    gain, f, b, GLq, HLq, Gq, Hq = R.best_split(H, nb, 1.0, 1.0, 0.0, 0.0)
+    assert (gain, f, b, GLq, HLq, Gq, Hq) == (0.5, 0, 1, 2, 4, 6, 8)
+    # with a positive lambda the same histogram is untouched by the rule: plain arithmetic
+    gain1, f1, b1 = R.best_split(H, nb, 1.0, 1.0, 1.0, 0.0)[:3]
+    cand = [(25.0 / 1.0 + 1.0 / 9.0) - 36.0 / 9.0, (4.0 / 5.0 + 16.0 / 5.0) - 36.0 / 9.0]
+    assert (gain1, f1, b1) == (cand[0], 0, 0)
+    # an empty node: every term is 0/0 -> 0, no candidate gains anything, no exception
+    gain0 = R.best_split(np.zeros((2, 256, 2), np.int64), np.array([4, 2], np.int32), 1.0, 1.0, 0.0, 0.0)[0]
+    assert gain0 == 0.0 and not R.accepts_split(gain0, 0.0)
+
+
+def test_params_validate_rejects_bad_regularisation():
+    gb.GBDTParams(reg_lambda=0.0, min_child_weight=0.0, gamma=0.0, scale_pos_weight=600.0).validate()
+    for kw in ({"reg_lambda": -1e-9}, {"reg_lambda": float("nan")}, {"reg_lambda": float("inf")},
+               {"min_child_weight": -1.0}, {"min_child_weight": float("inf")}, {"min_child_weight": float("nan")},
+               {"gamma": -0.5}, {"gamma": float("nan")}, {"gamma": float("inf")},
+               {"scale_pos_weight": 0.0}, {"scale_pos_weight": -2.0}, {"scale_pos_weight": float("nan")},
+               {"scale_pos_weight": float("inf")}):
+        with pytest.raises(ValueError):
+            gb.GBDTParams(**kw).validate()
+
+
+def test_kernel_test_oracles_agree_with_build_tree():
+    """tests/_gbdt_state.py's level oracles (histogram of built nodes, stable partition, split
+    decisions with sibling subtraction) chained over the levels reproduce R.build_tree."""
+    import _gbdt_state as S
+
+    X, y = _data(700, 5, seed=11)
+    cuts, nb = R.quantile_cuts(X, 16)
+    bins = R.bin_rows(X, cuts, nb)
+    gs, hs = R.grad_scales(2.0)
+    q = R.gradients(np.zeros(len(y), np.float32), y, 2.0, gs, hs)
+    depth, d = 4, 5
+    ref, leaf_idx = R.build_tree(bins, q, cuts, nb, depth, 1.0, 1.0, 0.0, 0.1, gs, hs)
+    st = S.level_state(0, [700], d=d, nbins=nb, depth=depth)
+    st.bins, st.gh = bins, q.astype(np.int16)
+    hist = np.zeros(((1 << depth) - 1, S.MAX_FEAT, 256, 2), np.int64)
+    feat = np.full((1 << depth) - 1, -1, np.int32)
+    binv = np.full((1 << depth) - 1, 255, np.int32)
+    for level in range(depth):
+        h0, nn = S.heap_first(level), 1 << level
+        ho = st.hist_oracle()
+        hist[h0:h0 + nn] = ho[h0:h0 + nn]
+        hist, f, b, t, g, _ = S.split_level_oracle(hist, st.gcnt, level, d, nb, cuts, 1 / gs, 1 / hs, 1.0, 1.0, 0.0)
+        feat[h0:h0 + nn], binv[h0:h0 + nn] = f, b
+        assert np.array_equal(f, ref.feat[h0:h0 + nn]) and np.array_equal(b, ref.bin[h0:h0 + nn])
+        assert np.array_equal(t, ref.thr[h0:h0 + nn]) and np.array_equal(g, ref.gain[h0:h0 + nn])
+        ridx, nid, _, seg, _, gcnt = S.partition_level(st, feat, binv)
+        st = S.LevelState(level + 1, depth, d, 700, (0, 0), nb, bins, st.gh, ridx, nid, seg, gcnt,
+                          seg[2 * h0 + 1:2 * h0 + 1 + 2 * nn, 1].copy())
+    assert np.array_equal(np.sort(st.ridx), np.arange(700))
+    assert np.array_equal(st.nid.astype(np.int64)[np.argsort(st.ridx)] - ((1 << depth) - 1), leaf_idx)

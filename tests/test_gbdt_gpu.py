@@ -54,6 +54,9 @@ def test_quantile_select_matches_sort(dev, n, d, sample, max_bin):
         X[:, 4] *= 1e-30
         X[::97, 5] = np.inf
         X[::89, 5] = -np.inf
+    if d > 7:
+        X[::53, 6] = np.nan                          # the radix key maps NaN last, as np.sort does
+        X[:, 7] = np.nan                             # every sample value NaN: a one-bin feature
     Xd = torch.from_numpy(X).to(dev)
     got = gb.quantile_cuts(Xd, max_bin, sample_rows=sample)
     per = max(1, sample)
@@ -89,6 +92,28 @@ def test_grad_kernel_matches_oracle(dev, spw):
     ref = R.gradients(margin, y, spw, gs, hs)
     diff = np.abs(gh.cpu().numpy().astype(np.int64) - ref)
     assert diff.max() <= 1 and (diff > 0).mean() < 1e-3
+
+
+@pytest.mark.parametrize("spw", [1.0, 37.5, 600.0])
+def test_grad_kernel_saturated_margins(dev, spw):
+    """Margins where exp saturates and the quantised Hessian reaches 0 (|margin| > ~12), among
+    ordinary ones: the same bound as above -- at most 1 quantum on fewer than 1e-3 of the rows."""
+    from fraud_detection_amd.ops.native import native, ptr, stream_of
+
+    rng = np.random.default_rng(2)
+    sat = np.array([0.0, -0.0, 12.0, -12.0, 40.0, -40.0, 88.0, -88.0, 200.0, -200.0], np.float32)
+    margin = np.concatenate([np.repeat(sat, 2), rng.normal(scale=3.0, size=49_980).astype(np.float32)])
+    y = np.concatenate([np.tile(np.array([0, 1], np.uint8), len(sat)), (rng.random(49_980) < 0.3).astype(np.uint8)])
+    n = len(margin)
+    gs, hs = R.grad_scales(spw)
+    md, yd = torch.from_numpy(margin).to(dev), torch.from_numpy(y).to(dev)
+    gh = torch.empty((n, 2), dtype=torch.int16, device=dev)
+    native().gbdt_grad(ptr(md), ptr(yd), n, spw, gs, hs, ptr(gh), stream_of(md))
+    ref = R.gradients(margin, y, spw, gs, hs)
+    assert (ref[4:20, 1] == 0).all() and (np.abs(ref[:, 0]) <= 1 << 14).all() and (ref[:, 1] <= 1 << 14).all()
+    diff = np.abs(gh.cpu().numpy().astype(np.int64) - ref)
+    assert diff.max() <= 1 and (diff > 0).mean() < 1e-3
+    assert diff[:20].max() == 0  # far from any rounding tie: exact
 
 
 @pytest.mark.parametrize("n,d,depth", [(60_000, 30, 5), (5_000, 7, 3), (777, 4, 6), (3_000, 5, 7)])
