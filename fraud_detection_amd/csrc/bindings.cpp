@@ -917,6 +917,11 @@ PYBIND11_MODULE(_fdx_native, m) {
   m.def("gbdt_grad", [](u margin, u label, int64_t n, float spw, float gscale, float hscale, u gh, u s) {
     fdx::launch_gbdt_grad(P<const float>(margin), P<const uint8_t>(label), n, spw, gscale, hscale, P<uint32_t>(gh), S(s));
   });
+  m.def("gbdt_grad_sampled", [](u margin, u label, int64_t n, float spw, float gscale, float hscale, u gh,
+                                uint64_t seed, int64_t round, int64_t row_offset, uint32_t threshold, u s) {
+    fdx::launch_gbdt_grad_sampled(P<const float>(margin), P<const uint8_t>(label), n, spw, gscale, hscale,
+                                  P<uint32_t>(gh), seed, round, row_offset, threshold, S(s));
+  });
   m.def("gbdt_hist_blocks", [] { return fdx::gbdt_hist_blocks(); });
   m.def("quantile_select_ws_bytes", [](int64_t m, int d) { return fdx::quantile_select_ws_bytes(m, d); });
   m.def("quantile_select", [](u X, int64_t m, int64_t stride, int ld, int d, int max_bin, u ws, u out, u s) {
@@ -942,11 +947,14 @@ PYBIND11_MODULE(_fdx_native, m) {
                                    hscale);
   });
   m.def("gbdt_split", [](u hist, u gcnt, int level, int d, u nbins, u cuts, double ginv, double hinv, double lam,
-                         double mcw, double gamma, u feat, u bin, u thr, u gain, u ng, u nh, u s) {
+                         double mcw, double gamma, u feat, u bin, u thr, u gain, u ng, u nh, u s, u fmask) {
     fdx::launch_gbdt_split(P<unsigned long long>(hist), P<const int64_t>(gcnt), level, d, P<const int>(nbins),
                            P<const float>(cuts), ginv, hinv, lam, mcw, gamma, P<int>(feat), P<int>(bin), P<float>(thr),
-                           P<double>(gain), P<long long>(ng), P<long long>(nh), S(s));
-  });
+                           P<double>(gain), P<long long>(ng), P<long long>(nh), S(s), P<const uint32_t>(fmask));
+  }, py::arg("hist"), py::arg("gcnt"), py::arg("level"), py::arg("d"), py::arg("nbins"), py::arg("cuts"),
+     py::arg("ginv"), py::arg("hinv"), py::arg("lam"), py::arg("mcw"), py::arg("gamma"), py::arg("feat"),
+     py::arg("bin"), py::arg("thr"), py::arg("gain"), py::arg("ng"), py::arg("nh"), py::arg("s"),
+     py::arg("fmask") = 0);
   m.def("gbdt_transpose", [](u bins, int64_t n, int d, u binsT, int64_t ldt, u s) {
     fdx::launch_gbdt_transpose(P<const uint8_t>(bins), n, d, P<uint8_t>(binsT), ldt, S(s));
   });
@@ -976,6 +984,13 @@ PYBIND11_MODULE(_fdx_native, m) {
     fdx::launch_gbdt_margin(P<const uint8_t>(binsT), ldt, n, P<const int>(feat), P<const int>(bin),
                             P<const float>(leaf), depth, P<float>(margin), P<const uint8_t>(label), spw, gscale,
                             hscale, P<uint32_t>(gh), S(s));
+  });
+  m.def("gbdt_margin_sampled", [](u binsT, int64_t ldt, int64_t n, u feat, u bin, u leaf, int depth, u margin,
+                                  u label, float spw, float gscale, float hscale, u gh, uint64_t seed, int64_t round,
+                                  int64_t row_offset, uint32_t threshold, u s) {
+    fdx::launch_gbdt_margin_sampled(P<const uint8_t>(binsT), ldt, n, P<const int>(feat), P<const int>(bin),
+                                    P<const float>(leaf), depth, P<float>(margin), P<const uint8_t>(label), spw,
+                                    gscale, hscale, P<uint32_t>(gh), seed, round, row_offset, threshold, S(s));
   });
   m.def("gbdt_eval", [](u margin, u label, int64_t r0, int64_t r1, u rec, u s) {
     fdx::launch_gbdt_eval(P<const float>(margin), P<const uint8_t>(label), r0, r1, P<long long>(rec), S(s));

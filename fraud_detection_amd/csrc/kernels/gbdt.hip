@@ -169,14 +169,44 @@ __device__ __forceinline__ int2 quantised_grad(float margin, bool pos, float spw
   return make_int2((int)rint(g * (double)gscale), (int)rint(h * (double)hscale));
 }
 
+// Row subsampling (stochastic boosting): table row r of round t is in the sample iff word
+// (r + row_offset) & 3 of philox4x32_10(lo32(R >> 2), hi32(R >> 2), t, kTagRow, k0, k1), R = r +
+// row_offset its global id, is below `thresh` = floor(subsample * 2^32) -- a stateless function of
+// (seed, round, global row), reference_gbdt.row_sample_mask.  An out-of-sample row's packed word is
+// 0: it adds nothing to any histogram, and nothing else of the round looks at the sample.  Every
+// row draws its group's four words itself: row_offset need not be a multiple of 4, so lane quads
+// and Philox groups do not line up, and 10 rounds of 32-bit multiplies are small against the fp64
+// sigmoid of an in-sample row.
+constexpr uint32_t kTagRow = 0x47425201u;  // reference_gbdt.TAG_ROW
+struct RowSample {
+  uint32_t k0, k1;      // lo32 / hi32 of the seed
+  uint32_t t;           // boosting round
+  uint32_t thresh;      // floor(subsample * 2^32), subsample < 1
+  int64_t row_offset;   // global id of table row 0
+};
+__device__ __forceinline__ bool row_in_sample(int64_t r, const RowSample& s) {
+  const uint64_t gr = (uint64_t)(r + s.row_offset), grp = gr >> 2;
+  const Philox4 p = philox4x32_10((uint32_t)grp, (uint32_t)(grp >> 32), s.t, kTagRow, s.k0, s.k1);
+  const uint32_t sub = (uint32_t)gr & 3u;
+  const uint32_t w = sub == 0 ? p.x : sub == 1 ? p.y : sub == 2 ? p.z : p.w;
+  return w < s.thresh;
+}
+
 // First round of a fit only: later rounds get their gradients from gbdt_margin_kernel<true>.
+// RS is empty without SAMPLE -- the unsampled kernel keeps its arguments -- and one RowSample with it.
+template <bool SAMPLE = false, typename... RS>
 __global__ __launch_bounds__(256) void gbdt_grad_kernel(const float* __restrict__ margin,
                                                         const uint8_t* __restrict__ label, int64_t n,
                                                         float spw, float gscale, float hscale,
-                                                        uint32_t* __restrict__ gh) {
+                                                        uint32_t* __restrict__ gh, RS... rs) {
+  static_assert(sizeof...(RS) == (SAMPLE ? 1 : 0), "a RowSample goes with SAMPLE, and only with it");
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    if constexpr (SAMPLE) {
+      if (!row_in_sample(i, rs...)) { gh[i] = 0u; continue; }
+    }
     gh[i] = pack_gh(quantised_grad(margin[i], label[i] != 0, spw, gscale, hscale));
+  }
 }
 
 // ---- histograms ------------------------------------------------------------------------------
@@ -657,9 +687,13 @@ __global__ __launch_bounds__(kHistThreads) void gbdt_split_kernel(
     const int* __restrict__ nbins, const float* __restrict__ cuts, double ginv, double hinv,
     double lambda, double min_child_weight, double gamma, int* __restrict__ tfeat,
     int* __restrict__ tbin, float* __restrict__ tthr, double* __restrict__ tgain,
-    long long* __restrict__ ng, long long* __restrict__ nh) {
+    long long* __restrict__ ng, long long* __restrict__ nh, const uint32_t* __restrict__ fmask) {
 #pragma clang fp contract(off)
   const int node = heap_first(level) + blockIdx.x;
+  // column subsampling: bit f of fmask[node] = feature f may be picked (null: every feature).  A
+  // masked-out feature loses only its candidate: its wave still stores a derived node's H = parent -
+  // sibling (the children subtract from it) and feature 0's wave still publishes the node totals.
+  const uint32_t allowed = fmask ? fmask[node] : 0xffffffffu;
   const int lane = lane_id(), wv = wave_id();
   constexpr int kW = kHistThreads / kWave;
   long long* H = reinterpret_cast<long long*>(hist) + (int64_t)node * kHistEntries;
@@ -731,7 +765,7 @@ __global__ __launch_bounds__(kHistThreads) void gbdt_split_kernel(
       if (og > best || (og == best && ob < bb)) { best = og; bb = ob; bgl = ogl; bhl = ohl; }
     }
     if (lane == 0) {
-      fgain[f] = best;
+      fgain[f] = ((allowed >> f) & 1u) ? best : -1.0e300;
       fbin[f] = bb;
       fgl[f] = bgl;
       fhl[f] = bhl;
@@ -1088,14 +1122,19 @@ __global__ void gbdt_leaf_kernel(const long long* __restrict__ ng, const long lo
 // per round at 6.4M rows against 61 us for this walk (profiles/r2_s4b).  The walk is bound by
 // the bins' line traffic -- the rows of a wave read up to 2^l feature columns at level l, ~200 MB
 // over a depth-5 walk -- so walking 4 rows per thread in lockstep measured slower (68-71 us).
-template <bool GRAD>
+// SAMPLE (with GRAD): the next round's row sample -- an out-of-sample row gets the word 0 and skips
+// the fp64 sigmoid; its margin is updated like every other row's.  RS as in gbdt_grad_kernel: empty
+// without SAMPLE, so the unsampled instantiations keep their arguments.
+template <bool GRAD, bool SAMPLE = false, typename... RS>
 __global__ __launch_bounds__(256) void gbdt_margin_kernel(const uint8_t* __restrict__ binsT, int64_t ldt,
                                                           int64_t n, const int* __restrict__ feat,
                                                           const int* __restrict__ bin,
                                                           const float* __restrict__ leaf, int depth,
                                                           float* __restrict__ margin,
                                                           const uint8_t* __restrict__ label, float spw,
-                                                          float gscale, float hscale, uint32_t* __restrict__ gh) {
+                                                          float gscale, float hscale, uint32_t* __restrict__ gh,
+                                                          RS... rs) {
+  static_assert(sizeof...(RS) == (SAMPLE ? 1 : 0) && (GRAD || !SAMPLE), "a RowSample goes with GRAD and SAMPLE only");
   __shared__ int sf[kGBMaxNodes], sb[kGBMaxNodes];
   __shared__ float sl[kGBMaxNodes + 1];
   const int ni = heap_first(depth);
@@ -1111,6 +1150,9 @@ __global__ __launch_bounds__(256) void gbdt_margin_kernel(const uint8_t* __restr
     for (int l = 0; l < depth; ++l) node = 2 * node + 1 + (int)goes_right(binsT, ldt, r, node, sf, sb);
     const float m = margin[r] + sl[node - ni];
     margin[r] = m;
+    if constexpr (GRAD && SAMPLE) {
+      if (!row_in_sample(r, rs...)) { gh[r] = 0u; continue; }
+    }
     if constexpr (GRAD) gh[r] = pack_gh(quantised_grad(m, label[r] != 0, spw, gscale, hscale));
   }
 }
@@ -1265,8 +1307,24 @@ void launch_gbdt_bin(const float* X, int64_t n, int ld, int d, const float* cuts
 void launch_gbdt_grad(const float* margin, const uint8_t* label, int64_t n, float spw, float gscale,
                       float hscale, uint32_t* gh, hipStream_t stream) {
   const int grid = stream_grid(n, 256, 4096);
-  gbdt_grad_kernel<<<grid, 256, 0, stream>>>(margin, label, n, spw, gscale, hscale, gh);
+  gbdt_grad_kernel<false><<<grid, 256, 0, stream>>>(margin, label, n, spw, gscale, hscale, gh);
   check_launch("gbdt_grad");
+}
+
+static RowSample row_sample(uint64_t seed, int64_t round, int64_t row_offset, int64_t n, uint32_t threshold,
+                            const char* what) {
+  if (round < 0 || round > 0xffffffffLL) throw std::runtime_error(std::string(what) + ": round outside [0, 2^32)");
+  if (row_offset < 0 || row_offset > INT64_MAX - n) throw std::runtime_error(std::string(what) + ": bad row_offset");
+  return RowSample{(uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)round, threshold, row_offset};
+}
+
+void launch_gbdt_grad_sampled(const float* margin, const uint8_t* label, int64_t n, float spw, float gscale,
+                              float hscale, uint32_t* gh, uint64_t seed, int64_t round, int64_t row_offset,
+                              uint32_t threshold, hipStream_t stream) {
+  const RowSample rs = row_sample(seed, round, row_offset, n, threshold, "gbdt_grad_sampled");
+  const int grid = stream_grid(n, 256, 4096);
+  gbdt_grad_kernel<true, RowSample><<<grid, 256, 0, stream>>>(margin, label, n, spw, gscale, hscale, gh, rs);
+  check_launch("gbdt_grad_sampled");
 }
 
 int gbdt_hist_blocks() {
@@ -1350,10 +1408,10 @@ void launch_gbdt_hist_l0_fused(const uint8_t* bins, uint32_t* gh, const int64_t*
 void launch_gbdt_split(unsigned long long* hist, const int64_t* gcnt, int level, int d, const int* nbins,
                        const float* cuts, double ginv, double hinv, double lambda,
                        double min_child_weight, double gamma, int* feat, int* bin, float* thr,
-                       double* gain, long long* ng, long long* nh, hipStream_t stream) {
+                       double* gain, long long* ng, long long* nh, hipStream_t stream, const uint32_t* fmask) {
   gbdt_split_kernel<<<1 << level, kHistThreads, 0, stream>>>(hist, gcnt, level, d, nbins, cuts, ginv, hinv,
                                                              lambda, min_child_weight, gamma, feat, bin,
-                                                             thr, gain, ng, nh);
+                                                             thr, gain, ng, nh, fmask);
   check_launch("gbdt_split");
 }
 
@@ -1405,6 +1463,19 @@ void launch_gbdt_margin(const uint8_t* binsT, int64_t ldt, int64_t n, const int*
     gbdt_margin_kernel<false><<<grid, 256, 0, stream>>>(binsT, ldt, n, feat, bin, leaf, depth, margin, label,
                                                         spw, gscale, hscale, gh);
   check_launch("gbdt_margin");
+}
+
+void launch_gbdt_margin_sampled(const uint8_t* binsT, int64_t ldt, int64_t n, const int* feat, const int* bin,
+                                const float* leaf, int depth, float* margin, const uint8_t* label, float spw,
+                                float gscale, float hscale, uint32_t* gh, uint64_t seed, int64_t round,
+                                int64_t row_offset, uint32_t threshold, hipStream_t stream) {
+  if (depth < 1 || depth > 7) throw std::runtime_error("gbdt_margin_sampled: depth must be in [1, 7]");
+  if (!gh) throw std::runtime_error("gbdt_margin_sampled: the sample applies to the gradients, gh is required");
+  const RowSample rs = row_sample(seed, round, row_offset, n, threshold, "gbdt_margin_sampled");
+  const int grid = stream_grid(n, 256, 4096);
+  gbdt_margin_kernel<true, true, RowSample><<<grid, 256, 0, stream>>>(binsT, ldt, n, feat, bin, leaf, depth, margin,
+                                                                      label, spw, gscale, hscale, gh, rs);
+  check_launch("gbdt_margin_sampled");
 }
 
 template <bool WALK>

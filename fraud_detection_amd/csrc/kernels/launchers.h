@@ -434,6 +434,12 @@ void launch_gbdt_bin(const float* X, int64_t n, int ld, int d, const float* cuts
                      uint8_t* bins, hipStream_t stream);
 void launch_gbdt_grad(const float* margin, const uint8_t* label, int64_t n, float spw, float gscale,
                       float hscale, uint32_t* gh, hipStream_t stream);
+// Row subsampling: table row r of round `round` keeps its gradients iff its Philox word (seed,
+// round, r + row_offset; reference_gbdt.row_sample_mask) is below threshold = floor(subsample * 2^32);
+// every other row's packed word is 0.
+void launch_gbdt_grad_sampled(const float* margin, const uint8_t* label, int64_t n, float spw, float gscale,
+                              float hscale, uint32_t* gh, uint64_t seed, int64_t round, int64_t row_offset,
+                              uint32_t threshold, hipStream_t stream);
 int gbdt_hist_blocks();
 // exact per-feature order statistics of the cut sample (quantile.hip): out [max_bin][d] holds the
 // minimum (row 0) and the values at ranks floor(t m / max_bin); rows r * stride of X [., ld]
@@ -458,7 +464,8 @@ void launch_gbdt_hist_l0_fused(const uint8_t* bins, uint32_t* gh, const int64_t*
 void launch_gbdt_split(unsigned long long* hist, const int64_t* gcnt, int level, int d, const int* nbins,
                        const float* cuts, double ginv, double hinv, double lambda,
                        double min_child_weight, double gamma, int* feat, int* bin, float* thr,
-                       double* gain, long long* ng, long long* nh, hipStream_t stream);
+                       double* gain, long long* ng, long long* nh, hipStream_t stream,
+                       const uint32_t* fmask = nullptr);  // [heap] allowed-feature bits per node; null: all
 // row-major [n][32] bins -> feature-major [d][ldt] (the partition's per-row feature reads)
 void launch_gbdt_transpose(const uint8_t* bins, int64_t n, int d, uint8_t* binsT, int64_t ldt, hipStream_t stream);
 void launch_gbdt_partition(const uint8_t* binsT, int64_t ldt, const int* ridx, const uint8_t* nid, int64_t n,
@@ -473,6 +480,11 @@ void launch_gbdt_leaf(const long long* ng, const long long* nh, int depth, doubl
 void launch_gbdt_margin(const uint8_t* binsT, int64_t ldt, int64_t n, const int* feat, const int* bin,
                         const float* leaf, int depth, float* margin, const uint8_t* label, float spw, float gscale,
                         float hscale, uint32_t* gh, hipStream_t stream);
+// gbdt_margin with gh, the gradients being those of round `round`'s row sample (gbdt_grad_sampled)
+void launch_gbdt_margin_sampled(const uint8_t* binsT, int64_t ldt, int64_t n, const int* feat, const int* bin,
+                                const float* leaf, int depth, float* margin, const uint8_t* label, float spw,
+                                float gscale, float hscale, uint32_t* gh, uint64_t seed, int64_t round,
+                                int64_t row_offset, uint32_t threshold, hipStream_t stream);
 // One round's validation record added into rec = int64 [4] (loss_q, n_err, n_pos, n_rows), exact
 // integers (gbdt.hip gbdt_eval_kernel): over rows [r0, r1) of an up-to-date margin, or (walk) over
 // an external eval set whose margin first takes the round's tree.  At most 2^27 rows.

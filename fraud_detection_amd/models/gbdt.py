@@ -46,14 +46,23 @@ class GBDTClassifier:
     def __init__(self, n_estimators: int = 100, learning_rate: float = 0.1, max_depth: int = 5,
                  reg_lambda: float = 1.0, min_child_weight: float = 1.0, gamma: float = 0.0, max_bin: int = 256,
                  scale_pos_weight: float = 1.0, base_score: float = 0.5, device: str = "auto",
-                 eval_metric=None, early_stopping_rounds: int | None = None, **_ignored):
-        # xgboost-only knobs the reference passes (objective, random_state, n_jobs) are accepted and
-        # ignored: the objective is binary:logistic, the fit is deterministic.  eval_metric and
-        # early_stopping_rounds are constructor arguments as in xgboost >= 1.6; they act only when
-        # fit() gets an eval_set (the reference's call passes none: nothing is evaluated).
+                 eval_metric=None, early_stopping_rounds: int | None = None, subsample: float = 1.0,
+                 colsample_bytree: float = 1.0, colsample_bylevel: float = 1.0, colsample_bynode: float = 1.0,
+                 seed: int | None = None, random_state: int | None = None, **_ignored):
+        # xgboost-only knobs the reference passes (objective, n_jobs) are accepted and ignored: the
+        # objective is binary:logistic.  eval_metric and early_stopping_rounds are constructor
+        # arguments as in xgboost >= 1.6; they act only when fit() gets an eval_set (the reference's
+        # call passes none: nothing is evaluated).  subsample / colsample_by* switch stochastic
+        # boosting on (ops/gbdt.fit_binned); ``random_state`` is the seed when ``seed`` is not given,
+        # and without sampling neither has any effect: the fit is deterministic.
+        if seed is None:
+            seed = 0 if random_state is None else random_state
         self.params = gb.GBDTParams(n_estimators=n_estimators, learning_rate=learning_rate, max_depth=max_depth,
                                     reg_lambda=reg_lambda, min_child_weight=min_child_weight, gamma=gamma,
-                                    max_bin=max_bin, scale_pos_weight=scale_pos_weight, base_score=base_score)
+                                    max_bin=max_bin, scale_pos_weight=scale_pos_weight, base_score=base_score,
+                                    subsample=subsample, colsample_bytree=colsample_bytree,
+                                    colsample_bylevel=colsample_bylevel, colsample_bynode=colsample_bynode,
+                                    seed=int(seed))
         self.device = device
         self.eval_metric = eval_metric
         self.early_stopping_rounds = early_stopping_rounds

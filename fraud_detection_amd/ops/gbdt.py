@@ -38,8 +38,33 @@ class GBDTParams:
     scale_pos_weight: float = 1.0
     base_score: float = 0.5
     cut_sample_rows: int = 1 << 20
+    # stochastic boosting: stateless Philox draws of (seed, round, global row | feature),
+    # reference_gbdt.row_sample_mask / feature_masks.  With every fraction at 1.0 the seed has no
+    # effect and the fit is the deterministic full-data fit, launch for launch.
+    subsample: float = 1.0
+    colsample_bytree: float = 1.0
+    colsample_bylevel: float = 1.0
+    colsample_bynode: float = 1.0
+    seed: int = 0
+
+    SAMPLING_DEFAULTS = {"subsample": 1.0, "colsample_bytree": 1.0, "colsample_bylevel": 1.0,
+                         "colsample_bynode": 1.0, "seed": 0}
+
+    @property
+    def colsampled(self) -> bool:
+        return not (self.colsample_bytree == 1.0 and self.colsample_bylevel == 1.0 and self.colsample_bynode == 1.0)
+
+    @property
+    def sampled(self) -> bool:
+        return self.subsample != 1.0 or self.colsampled
 
     def validate(self):
+        for name in ("subsample", "colsample_bytree", "colsample_bylevel", "colsample_bynode"):
+            v = float(getattr(self, name))
+            if not 0.0 < v <= 1.0:  # NaN fails too
+                raise ValueError(f"{name} must be in (0, 1]")
+        if isinstance(self.seed, bool) or not isinstance(self.seed, (int, np.integer)) or not 0 <= int(self.seed) < 1 << 64:
+            raise ValueError("seed must be an integer in [0, 2^64)")
         if not 1 <= self.max_depth <= 7:
             raise ValueError("max_depth must be in [1, 7] (node ids are stored in one byte)")
         if not 2 <= self.max_bin <= MAX_BIN:
@@ -371,7 +396,8 @@ def _resume(checkpoint, sig, T):
 def fit(X: torch.Tensor, y: torch.Tensor, params: GBDTParams | None = None, comm=None,
         cuts=None, sample_weight_pos: float | None = None, return_margin: bool = False,
         checkpoint=None, checkpoint_every: int = 10, use_graph: bool | None = None,
-        eval_set=None, eval_metric=("logloss",), early_stopping_rounds: int | None = None):
+        eval_set=None, eval_metric=("logloss",), early_stopping_rounds: int | None = None,
+        row_offset: int | None = None):
     """Boost `n_estimators` depth-D trees on standardized float32 rows X [n, d] with labels y.
 
     ``checkpoint``: a utils.checkpoint.CheckpointManager.  Every ``checkpoint_every`` rounds the
@@ -379,8 +405,8 @@ def fit(X: torch.Tensor, y: torch.Tensor, params: GBDTParams | None = None, comm
     round.  Training margins are recomputed from the saved trees over the same bins, so a resumed
     fit is bit-identical to an uninterrupted one.
 
-    ``eval_set`` / ``eval_metric`` / ``early_stopping_rounds``: see fit_binned; with an eval set
-    the return value gains an EvalRecord as its last element."""
+    ``eval_set`` / ``eval_metric`` / ``early_stopping_rounds`` / ``row_offset``: see fit_binned; with
+    an eval set the return value gains an EvalRecord as its last element."""
     p = (params or GBDTParams()).validate()
     n, d = X.shape
     if d > MAX_FEAT:
@@ -390,13 +416,15 @@ def fit(X: torch.Tensor, y: torch.Tensor, params: GBDTParams | None = None, comm
     bins = bin_rows(X, cuts[0], cuts[1])
     return fit_binned(bins, y, cuts, p, comm=comm, sample_weight_pos=sample_weight_pos, return_margin=return_margin,
                       checkpoint=checkpoint, checkpoint_every=checkpoint_every, use_graph=use_graph,
-                      eval_set=eval_set, eval_metric=eval_metric, early_stopping_rounds=early_stopping_rounds)
+                      eval_set=eval_set, eval_metric=eval_metric, early_stopping_rounds=early_stopping_rounds,
+                      row_offset=row_offset)
 
 
 def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | None = None, comm=None,
                sample_weight_pos: float | None = None, return_margin: bool = False, checkpoint=None,
                checkpoint_every: int = 10, use_graph: bool | None = None, hole: tuple | None = None,
-               eval_set=None, eval_metric=("logloss",), early_stopping_rounds: int | None = None):
+               eval_set=None, eval_metric=("logloss",), early_stopping_rounds: int | None = None,
+               row_offset: int | None = None):
     """Boosting on already-binned rows (u8 [n, 32], bin_rows) with their cuts (cuts, nbins).
 
     ``hole``: (at, len) -- the fit's rows are the table without the block [at, at + len) (a
@@ -421,7 +449,24 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
     returned margin is rebuilt from the kept trees by the round's own margin kernel, so it equals
     their walk bit for bit.  With an eval set the return value gains an EvalRecord as its last
     element.  Under data-parallel training every rank passes its shard of the eval rows and the
-    integer records are all-reduced, so all ranks stop at the same round."""
+    integer records are all-reduced, so all ranks stop at the same round.
+
+    Stochastic boosting (``subsample``, ``colsample_bytree`` / ``_bylevel`` / ``_bynode``, ``seed`` of
+    GBDTParams): round t's trees see the gradients of the sampled rows only -- an out-of-sample row's
+    quantised (g, h) is 0, so it adds nothing to any histogram -- and a node's split scan may pick
+    only the node's sampled features.  Every table row still takes every tree's margin update, and
+    evaluation, early stopping and the returned margins are those of the full rows, as in xgboost.
+    The draws are stateless Philox functions of (seed, round, global row id | feature)
+    (reference_gbdt.row_sample_mask / feature_masks), so repeated fits and resumed fits are bitwise
+    equal and a fold keeps its draws around a ``hole`` (a row keeps its TABLE index).  ``row_offset``:
+    the global id of table row 0; None is 0, or under ``comm`` the sum of the lower ranks' table
+    rows, so contiguous shards in rank order grow the single-process trees.  The feature masks of
+    all rounds are drawn on the host and uploaded once; no round waits for the host.  With any
+    sampling on, the opt-in hipGraph path (FDX_GBDT_GRAPH=1 / use_graph) and FDX_GBDT_FUSE_MARGIN=1
+    fall back to the eager, unfused round: the round number t, which selects the row sample and the
+    row of the mask table, is a launch argument that changes every round: a captured graph would
+    replay the value of the round it was recorded in, and the fused level-0 pass (gbdt_hist_l0_fused)
+    computes the gradients itself and has no sampled variant."""
     p = (params or GBDTParams()).validate()
     cuts_np, nbins = cuts
     d = int(len(nbins))
@@ -440,7 +485,20 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
     ni, nl = (1 << D) - 1, 1 << D
     T = p.n_estimators
     base_margin = float(np.log(p.base_score / (1.0 - p.base_score)))
-    ens_kw = dict(depth=D, cuts=cuts_np, nbins=nbins, base_score=p.base_score, params=dict(p.__dict__))
+    dist = comm is not None and comm.world_size > 1
+    sub_on, seed = p.subsample != 1.0, int(p.seed)
+    thresh = R.sample_threshold(p.subsample) if sub_on else 0
+    if row_offset is None:
+        row_offset = 0
+        if sub_on and dist:
+            row_offset = int(sum(r[0] for r in comm.all_gather_ints([n])[:comm.rank]))
+    row_offset = int(row_offset)
+    if row_offset < 0 or row_offset + n >= 1 << 62:
+        raise ValueError("row_offset must be >= 0 (and the global row ids below 2^62)")
+    # allowed-feature bits of every (round, heap node), drawn on the host once per fit
+    fmasks = R.feature_mask_table(seed, T, d, D, p.colsample_bytree, p.colsample_bylevel,
+                                  p.colsample_bynode) if p.colsampled else None
+    ens_kw = dict(depth=D, cuts=cuts_np, nbins=nbins, base_score=p.base_score, params={**p.__dict__, "seed": seed})
     req = _eval_request(eval_set, eval_metric, early_stopping_rounds, hl, checkpoint,
                         comm is not None and comm.world_size > 1, T)
     ev = None
@@ -463,8 +521,21 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
         from ..utils.checkpoint import config_signature
 
         n_all = int(comm.all_reduce_scalar(float(n_fit))) if (comm is not None and comm.world_size > 1) else n_fit
-        sig = config_signature(params={k: v for k, v in p.__dict__.items() if k != "n_estimators"}, spw=spw,
-                               cuts=cuts_np, nbins=nbins, n=n_all, d=d, **({"hole": [ha, hl]} if hl else {}))
+        # the sampling fields only where they differ from their defaults: checkpoints written before
+        # they existed still resume
+        dflt = p.SAMPLING_DEFAULTS
+        sig_params = {k: v for k, v in p.__dict__.items()
+                      if k != "n_estimators" and not (k in dflt and v == dflt[k])}
+        # Which global rows the fit draws for is part of a sampled fit's configuration.  Every rank
+        # must compute the SAME signature (rank 0 writes the checkpoint, all ranks load it), so
+        # under data parallelism it names every rank's offset, not this rank's.
+        offs = {}
+        if sub_on and dist:
+            offs = {"row_offsets": [int(r[0]) for r in comm.all_gather_ints([row_offset])]}
+        elif sub_on and row_offset:
+            offs = {"row_offset": row_offset}
+        sig = config_signature(params=sig_params, spw=spw,
+                               cuts=cuts_np, nbins=nbins, n=n_all, d=d, **({"hole": [ha, hl]} if hl else {}), **offs)
     prev, t0 = _resume(checkpoint, sig, T)
 
     def _save(t_done, feat, binv, thr, gain, leaf):
@@ -492,8 +563,10 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
             m_ev = np.full(b_ev.shape[0], np.float32(base_margin), np.float32)
         for t in range(t0, T):
             q = R.gradients(margin, yy, spw, gscale, hscale)
+            if sub_on:  # global ids of the fit's rows: a row keeps its table index around the hole
+                q[~R.row_sample_mask(seed, t, keep + row_offset, p.subsample)] = 0
             tr, node = R.build_tree(b, q, cuts_np, nbins, D, p.reg_lambda, p.min_child_weight, p.gamma,
-                                    p.learning_rate, gscale, hscale, comm)
+                                    p.learning_rate, gscale, hscale, comm, None if fmasks is None else fmasks[t])
             feat[t], binv[t], thr[t], gain[t], leaf[t] = tr.feat, tr.bin, tr.thr, tr.gain, tr.leaf
             margin = (margin + tr.leaf[node]).astype(np.float32)
             if (t + 1) % max(1, checkpoint_every) == 0 or t + 1 == T:
@@ -530,7 +603,6 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
     binsT = torch.empty(d * ldt, dtype=torch.uint8, device=dev)
     if n:
         m.gbdt_transpose(ptr(bins), n, d, ptr(binsT), ldt, st0)
-    dist = comm is not None and comm.world_size > 1
     n_global = int(comm.all_reduce_scalar(float(n_fit))) if dist else n_fit
     ct = torch.from_numpy(np.ascontiguousarray(cuts_np[:d])).to(dev)
     nt = torch.from_numpy(np.ascontiguousarray(nbins[:d])).to(dev)
@@ -548,22 +620,29 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
                           gscale, hscale, 0, st0)
     lam, mcw, gam = float(p.reg_lambda), float(p.min_child_weight), float(p.gamma)
     ginv, hinv = 1.0 / gscale, 1.0 / hscale
+    # [T, ni] uint32 bits, rows contiguous: a split launch gets the address of its round's row
+    fm_dev = torch.from_numpy(np.ascontiguousarray(fmasks).view(np.int32)).to(dev) if fmasks is not None else None
 
     def round_body(o_feat, o_bin, o_thr, o_gain, o_leaf, grad_first=False, grad_next=True, prev=None,
-                   defer_margin=False):
+                   defer_margin=False, t=0):
         """One boosting round: a fixed launch sequence with static pointers (graph-capturable).
         The gradients of a round come from the previous round's margin update (gbdt_margin with
         gh), so only the first round of a fit launches gbdt_grad.  ``prev`` (feat, bin, leaf of the
         previous tree, its margin walk deferred): level 0 runs that walk fused in front of its
-        histogram (gbdt_hist_l0_fused).  ``defer_margin``: leave this tree's walk to the next round."""
+        histogram (gbdt_hist_l0_fused).  ``defer_margin``: leave this tree's walk to the next round.
+        ``t``: the round, read only under sampling (round t's row sample goes into the gradients
+        that round t - 1's margin walk writes; round t's feature masks into its split scans)."""
         st = stream_of(bins)  # the capture stream while a hipGraph is being recorded
-        if grad_first:
+        if grad_first and sub_on:
+            m.gbdt_grad_sampled(ptr(margin), ptr(y), n, spw, gscale, hscale, ptr(ws.gh), seed, t, row_offset, thresh, st)
+        elif grad_first:
             m.gbdt_grad(ptr(margin), ptr(y), n, spw, gscale, hscale, ptr(ws.gh), st)
         # zero histograms and per-node counts, root segment + global count: one launch (level 0
         # reads rows in order, so ridx / nid need no iota / root fill)
         m.gbdt_round_init(ptr(ws.hist), ws.hist.numel(), ptr(ws.seg), ptr(ws.gcnt), n_fit, n_global, st,
                           ptr(ws.node_r), ws.node_r.numel())
         cur = 0
+        fmask_arg = () if fm_dev is None else (ptr(fm_dev[t]),)  # the round's [ni] mask row; none: every feature
         for level in range(D):
             h0, nn = (1 << level) - 1, 1 << level
             if level == 0 and prev is not None:
@@ -576,7 +655,7 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
             if dist:
                 comm.all_reduce_(ws.hist[h0 * HIST_ENTRIES:(h0 + nn) * HIST_ENTRIES])
             m.gbdt_split(ptr(ws.hist), ptr(ws.gcnt), level, d, ptr(nt), ptr(ct), ginv, hinv, lam, mcw, gam,
-                         ptr(o_feat), ptr(o_bin), ptr(o_thr), ptr(o_gain), ptr(ws.ng), ptr(ws.nh), st)
+                         ptr(o_feat), ptr(o_bin), ptr(o_thr), ptr(o_gain), ptr(ws.ng), ptr(ws.nh), st, *fmask_arg)
             if level == D - 1:
                 break  # leaves: the margin walk and gbdt_leaf (split-kernel child sums) need no partition
             if n_fit:
@@ -592,7 +671,10 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
             if dist:
                 comm.all_reduce_(ws.gcnt[c0:c0 + 2 * nn])
         m.gbdt_leaf(ptr(ws.ng), ptr(ws.nh), D, ginv, hinv, lam, mcw, float(p.learning_rate), ptr(o_leaf), st)
-        if n and not defer_margin:
+        if n and not defer_margin and grad_next and sub_on:
+            m.gbdt_margin_sampled(ptr(binsT), ldt, n, ptr(o_feat), ptr(o_bin), ptr(o_leaf), D, ptr(margin), ptr(y), spw,
+                                  gscale, hscale, ptr(ws.gh), seed, t + 1, row_offset, thresh, st)
+        elif n and not defer_margin:
             m.gbdt_margin(ptr(binsT), ldt, n, ptr(o_feat), ptr(o_bin), ptr(o_leaf), D, ptr(margin), ptr(y), spw,
                           gscale, hscale, ptr(ws.gh) if grad_next else 0, st)
 
@@ -611,8 +693,11 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
     # Evaluation keeps the eager launches: a round is followed by the eval kernel, a record copy and
     # an event, and the stop rule may end the fit between two rounds.  The deferred margin walk is
     # off too (the hole's margins must be current when the round's record is taken).
-    graphable = use_graph and not dist and n > 0 and T - t0 >= 3 and ev is None
-    fuse_margin = os.environ.get("FDX_GBDT_FUSE_MARGIN", "0") == "1" and not graphable and ev is None
+    # Sampling keeps them too, unfused: a recorded round and the fused level-0 pass bake the round's
+    # constants in, and the round number (row sample, mask row) is one of them.
+    graphable = use_graph and not dist and n > 0 and T - t0 >= 3 and ev is None and not p.sampled
+    fuse_margin = (os.environ.get("FDX_GBDT_FUSE_MARGIN", "0") == "1" and not graphable and ev is None
+                   and not p.sampled)
     graph = None
     if ev is not None:
         from . import metrics as metric_ops
@@ -691,7 +776,7 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
             fuse = fuse_margin and n_fit > 0
             round_body(feat[t], binv[t], thr[t], gain[t], leaf[t], grad_first=(t == t0), grad_next=(t + 1 < T),
                        prev=(feat[t - 1], binv[t - 1], leaf[t - 1]) if (fuse and t > t0) else None,
-                       defer_margin=fuse and t + 1 < T)
+                       defer_margin=fuse and t + 1 < T, t=t)
         after_round(t)
         if ev is not None:
             eval_round(t)

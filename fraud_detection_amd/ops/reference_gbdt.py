@@ -117,8 +117,11 @@ class TreeArrays:
     leaf: np.ndarray   # [nl] float32
 
 
-def best_split(H: np.ndarray, nbins: np.ndarray, ginv: float, hinv: float, lam: float, mcw: float):
-    """H: int64 [d, 256, 2] of one node.  Returns (gain, feature, bin, GLq, HLq, Gq, Hq)."""
+def best_split(H: np.ndarray, nbins: np.ndarray, ginv: float, hinv: float, lam: float, mcw: float,
+               fmask: int | None = None):
+    """H: int64 [d, 256, 2] of one node.  Returns (gain, feature, bin, GLq, HLq, Gq, Hq).
+    ``fmask``: bit f set = feature f may be picked (None: all).  The node totals come from feature
+    0's sums whether or not feature 0 is allowed; with no valid allowed split the gain is -inf."""
     d = H.shape[0]
     cg = np.cumsum(H[:, :, 0], axis=1)
     chs = np.cumsum(H[:, :, 1], axis=1)
@@ -134,6 +137,8 @@ def best_split(H: np.ndarray, nbins: np.ndarray, ginv: float, hinv: float, lam: 
         gain = (np.where(dl > 0.0, GL * GL / dl, 0.0) + np.where(dr > 0.0, GR * GR / dr, 0.0)) - root
     b = np.arange(MAX_BIN)[None, :]
     valid = (b < (nbins[:d, None] - 1)) & (HL >= mcw) & (HR >= mcw)
+    if fmask is not None:
+        valid &= ((int(fmask) >> np.arange(d)) & 1).astype(bool)[:, None]
     gain = np.where(valid, gain, -np.inf)
     flat = int(np.argmax(gain))
     f, bb = divmod(flat, MAX_BIN)
@@ -141,8 +146,9 @@ def best_split(H: np.ndarray, nbins: np.ndarray, ginv: float, hinv: float, lam: 
 
 
 def build_tree(bins: np.ndarray, q: np.ndarray, cuts: np.ndarray, nbins: np.ndarray, depth: int, lam: float,
-               mcw: float, gamma: float, eta: float, gscale: float, hscale: float, comm=None):
-    """Grow one depth-`depth` heap tree.  Returns (TreeArrays, leaf index per row [n])."""
+               mcw: float, gamma: float, eta: float, gscale: float, hscale: float, comm=None, fmasks=None):
+    """Grow one depth-`depth` heap tree.  Returns (TreeArrays, leaf index per row [n]).
+    ``fmasks``: uint32 [2^depth - 1] allowed-feature bits per heap node (feature_masks), or None."""
     n = bins.shape[0]
     d = int(len(nbins))
     ginv, hinv = 1.0 / gscale, 1.0 / hscale
@@ -165,7 +171,8 @@ def build_tree(bins: np.ndarray, q: np.ndarray, cuts: np.ndarray, nbins: np.ndar
         right = np.zeros(n, bool)
         for k in range(nn):
             hid = h0 + k
-            g_, f, b, GLq, HLq, Gq, Hq = best_split(Hl[k], nbins, ginv, hinv, lam, mcw)
+            g_, f, b, GLq, HLq, Gq, Hq = best_split(Hl[k], nbins, ginv, hinv, lam, mcw,
+                                                        None if fmasks is None else int(fmasks[hid]))
             if hid == 0:
                 ng[0], nh[0] = Gq, Hq
             split = accepts_split(g_, gamma)
@@ -196,6 +203,115 @@ def leaf_values(ng: np.ndarray, nh: np.ndarray, depth: int, ginv: float, hinv: f
         w = 0.0 if (H < mcw or H <= 0.0) else -G / (H + lam)
         leaf[i] = np.float32(eta * w)
     return leaf
+
+
+# ---- stochastic boosting: stateless Philox draws ----------------------------------------------------
+# Every draw is a pure function of (seed, round, global row | feature): repeated fits, data-parallel
+# shards, checkpoint resumes and folds around a row hole all see the same bits.  The tags separate
+# the four streams (counter word c3); gbdt.hip mirrors TAG_ROW.
+TAG_ROW = 0x47425201
+TAG_TREE = 0x47425402
+TAG_LEVEL = 0x47424C03
+TAG_NODE = 0x47424E04
+
+
+def sample_threshold(subsample: float) -> int:
+    """floor(subsample * 2^32) in fp64: a row is in the sample iff its 32-bit word is below it."""
+    return int(np.floor(float(subsample) * 4294967296.0))
+
+
+def row_sample_mask(seed: int, t: int, rows, subsample: float) -> np.ndarray:
+    """bool [len(rows)]: which GLOBAL row ids (int64) are in round t's sample.  Row r takes word
+    r & 3 of philox4x32_10(lo32(r >> 2), hi32(r >> 2), t, TAG_ROW, lo32(seed), hi32(seed)), so one
+    call serves 4 consecutive rows."""
+    from .reference import philox4x32_10
+
+    rows = np.asarray(rows, dtype=np.int64)
+    grp = (rows >> 2).astype(np.uint64)
+    seed = int(seed)
+    w = philox4x32_10((grp & np.uint64(0xFFFFFFFF)).astype(np.uint32), (grp >> np.uint64(32)).astype(np.uint32),
+                      np.full(rows.shape, int(t) & 0xFFFFFFFF, np.uint32), np.full(rows.shape, TAG_ROW, np.uint32),
+                      seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
+    word = np.choose(rows & 3, w) if rows.size else np.zeros(0, np.uint32)
+    return word.astype(np.uint64) < np.uint64(sample_threshold(subsample))
+
+
+def _colsample_stage(cand: list, frac: float, keys: np.ndarray) -> list:
+    """The max(1, int(frac * len(cand))) features of `cand` with the smallest (key, feature)."""
+    if frac == 1.0:
+        return cand
+    k = max(1, int(frac * len(cand)))
+    return sorted(sorted(cand, key=lambda f: (int(keys[f]), f))[:k])
+
+
+def feature_masks(seed: int, t: int, d: int, depth: int, bytree: float = 1.0, bylevel: float = 1.0,
+                  bynode: float = 1.0) -> np.ndarray:
+    """uint32 [2^depth - 1]: the allowed-feature bits of every heap node of round t's tree.  Three
+    nested stages as in xgboost (node within level within tree); a stage with fraction c over the
+    candidates C keeps the max(1, int(c * len(C))) features with the smallest (key, f),
+    key = philox4x32_10(f, idx, t, TAG, lo32(seed), hi32(seed)).x with (idx, TAG) = (0, TAG_TREE),
+    (level, TAG_LEVEL), (heap id, TAG_NODE).  A stage at 1.0 passes its set through without a draw."""
+    from .reference import philox4x32_10
+
+    seed = int(seed)
+    k0, k1 = seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF
+    ni = (1 << depth) - 1
+
+    def keys(idx, tag):  # [len(idx), d] uint32
+        idx = np.asarray(idx, np.uint32)
+        shape = (idx.shape[0], d)
+        f = np.broadcast_to(np.arange(d, dtype=np.uint32)[None, :], shape)
+        return philox4x32_10(f, np.broadcast_to(idx[:, None], shape), np.full(shape, int(t) & 0xFFFFFFFF, np.uint32),
+                             np.full(shape, tag, np.uint32), k0, k1)[0]
+
+    tree = _colsample_stage(list(range(d)), bytree, keys([0], TAG_TREE)[0] if bytree != 1.0 else None)
+    lkeys = keys(np.arange(depth), TAG_LEVEL) if bylevel != 1.0 else None
+    nkeys = keys(np.arange(ni), TAG_NODE) if bynode != 1.0 else None
+    out = np.zeros(ni, np.uint32)
+    for level in range(depth):
+        lset = _colsample_stage(tree, bylevel, None if lkeys is None else lkeys[level])
+        for hid in range((1 << level) - 1, (2 << level) - 1):
+            nset = _colsample_stage(lset, bynode, None if nkeys is None else nkeys[hid])
+            out[hid] = sum(1 << f for f in nset)
+    return out
+
+
+def feature_mask_table(seed: int, rounds: int, d: int, depth: int, bytree: float = 1.0, bylevel: float = 1.0,
+                       bynode: float = 1.0) -> np.ndarray:
+    """uint32 [rounds, 2^depth - 1]: feature_masks of rounds 0 .. rounds - 1, what a fit draws once
+    (and uploads once).  The same draws taken for all rounds at a time: a stage is one Philox call
+    over [round, index, feature] and one sort of (key << 5 | feature) with the non-candidates pushed
+    to the end -- the candidate count of a stage is the same in every round and node."""
+    from .reference import philox4x32_10
+
+    seed = int(seed)
+    k0, k1 = seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF
+    ni = (1 << depth) - 1
+    fbits = np.uint32(1) << np.arange(d, dtype=np.uint32)
+    if rounds == 0:
+        return np.zeros((0, ni), np.uint32)
+
+    def stage(cand, frac, idx, tag):  # cand: bool [rounds, len(idx) or 1, d]
+        cand = np.broadcast_to(cand, (rounds, len(idx), d))
+        if frac == 1.0:
+            return cand
+        k = max(1, int(frac * int(cand[0, 0].sum())))
+        shape = cand.shape
+        f = np.broadcast_to(np.arange(d, dtype=np.uint32), shape)
+        key = philox4x32_10(f, np.broadcast_to(np.asarray(idx, np.uint32)[None, :, None], shape),
+                            np.broadcast_to(np.arange(rounds, dtype=np.uint32)[:, None, None], shape),
+                            np.full(shape, tag, np.uint32), k0, k1)[0]
+        comp = np.where(cand, (key.astype(np.uint64) << np.uint64(5)) | f.astype(np.uint64), np.uint64(2 ** 64 - 1))
+        out = np.zeros(shape, bool)
+        np.put_along_axis(out, np.argsort(comp, axis=-1, kind="stable")[..., :k], True, axis=-1)
+        return out
+
+    tree = stage(np.ones((rounds, 1, d), bool), bytree, [0], TAG_TREE)
+    level = stage(tree, bylevel, np.arange(depth), TAG_LEVEL)
+    node_level = np.floor(np.log2(np.arange(ni) + 1)).astype(np.int64)  # heap id -> level
+    node = stage(level[:, node_level, :], bynode, np.arange(ni), TAG_NODE)
+    # C-contiguous whatever layout the indexing above left: row t is what round t's split launches read
+    return np.ascontiguousarray((node * fbits).sum(-1, dtype=np.uint32))
 
 
 LOSS_CAP = 36.841361487904734  # -ln(1e-16): xgboost clamps p to [eps, 1 - eps], eps = 1e-16

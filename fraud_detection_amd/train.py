@@ -54,14 +54,18 @@ def _shard(idx: np.ndarray, comm) -> np.ndarray:
 
 def run(settings: Settings | None = None, model_type: str = "logistic", cv_folds: int = 5, model_dir: str = "models",
         verbose: bool = True, cfg: TrainConfig | None = None, comm=None, gbdt_eval_metric=None,
-        gbdt_early_stopping: int | None = None) -> dict:
+        gbdt_early_stopping: int | None = None, gbdt_subsample: float = 1.0, gbdt_colsample_bytree: float = 1.0,
+        gbdt_seed: int = 0) -> dict:
     """Single process, or data parallel when ``comm`` spans several ranks (torchrun: one rank per
     GPU).  Every rank reads the table and derives the same split; each fits on its strided shard
     with RCCL all-reduced statistics, so all ranks hold the same model; rank 0 writes artifacts.
 
     ``gbdt_eval_metric`` / ``gbdt_early_stopping``: per-round validation metrics of every CV fold
     and early stopping in the device GBDT CV job (models/gbdt_cv.DeviceGBDTCV); the curves, best
-    rounds and the final fit's round count land in the summary under "gbdt_eval"."""
+    rounds and the final fit's round count land in the summary under "gbdt_eval".
+
+    ``gbdt_subsample`` / ``gbdt_colsample_bytree`` / ``gbdt_seed``: stochastic boosting of the GBDT
+    family (ops/gbdt.GBDTParams), in every CV fold and in the final fit alike."""
     s = settings or Settings.load()
     comm = comm if (comm is not None and comm.world_size > 1) else None
     lead = comm is None or comm.rank == 0
@@ -105,12 +109,20 @@ def run(settings: Settings | None = None, model_type: str = "logistic", cv_folds
     cfg = cfg or TrainConfig(solver=s.solver, storage=s.dtype, seed=s.seed, k_neighbors=s.smote_k)
     if model_type not in ("logistic", "gbdt"):
         raise ValueError("model_type must be 'logistic' or 'gbdt'")
+    gbdt_params = None
+    if model_type == "gbdt":
+        from .ops.gbdt import GBDTParams
+
+        gbdt_params = GBDTParams(subsample=gbdt_subsample, colsample_bytree=gbdt_colsample_bytree,
+                                 seed=gbdt_seed).validate()
+    elif (gbdt_subsample, gbdt_colsample_bytree, gbdt_seed) != (1.0, 1.0, 0):
+        raise ValueError("--gbdt-subsample / --gbdt-colsample-bytree / --gbdt-seed need --model gbdt")
     cv_scores = []
     from dataclasses import asdict
 
     ck_dir = s.checkpoint_dir or None
     progress = _Progress(ck_dir, lead, signature=None if ck_dir is None else _job_signature(
-        s, model_type, cv_folds, mode, asdict(cfg), X.shape, comm))
+        s, model_type, cv_folds, mode, asdict(cfg), X.shape, comm, gbdt_params))
     if progress.folds:
         say(f" Resuming: {len(progress.folds)} completed fold(s) from {progress.path}")
     res_cv = None
@@ -157,7 +169,7 @@ def run(settings: Settings | None = None, model_type: str = "logistic", cv_folds
 
             t_fit = time.perf_counter()
             with tracing.span("train.cv_job", model=model_type), tracing.roctx_range("train.cv_job"):
-                cvr = DeviceGBDTCV(cfg, n_folds=cv_folds, seed=42, eval_metric=gbdt_eval_metric,
+                cvr = DeviceGBDTCV(cfg, params=gbdt_params, n_folds=cv_folds, seed=42, eval_metric=gbdt_eval_metric,
                                    early_stopping_rounds=gbdt_early_stopping).run(Xtr, ytr, fold_codes=job_codes)
             cv_scores, res_cv, cv_engine = cvr.fold_aucs, cvr.final, "device"
             if cvr.fold_evals:
@@ -169,7 +181,7 @@ def run(settings: Settings | None = None, model_type: str = "logistic", cv_folds
             for k, auc in enumerate(cv_scores):
                 progress.record(k, auc)
         else:
-            cv_scores = _cross_validate(model_type, cfg, folds, take, comm, cv_mode, progress)
+            cv_scores = _cross_validate(model_type, cfg, folds, take, comm, cv_mode, progress, gbdt_params)
             cv_engine = f"per_fold:{cv_mode}"
         for k, auc in enumerate(cv_scores):
             say(f"  Fold {k + 1} AUC: {auc:.4f}")
@@ -179,7 +191,8 @@ def run(settings: Settings | None = None, model_type: str = "logistic", cv_folds
         t_fit = time.perf_counter()
         with tracing.span("train.final_fit", model=model_type), tracing.roctx_range("train.final_fit"):
             res = _fit(model_type, cfg, Xtr, ytr, comm,
-                       checkpoint=None if ck_dir is None else os.path.join(ck_dir, f"final_{model_type}"))
+                       checkpoint=None if ck_dir is None else os.path.join(ck_dir, f"final_{model_type}"),
+                       gbdt_params=gbdt_params)
             if dev.type == "cuda":
                 torch.cuda.synchronize(dev)
     else:
@@ -215,6 +228,9 @@ def run(settings: Settings | None = None, model_type: str = "logistic", cv_folds
                "seconds": round(time.time() - t0, 3), "registered_version": None}
     if gbdt_eval is not None:
         summary["gbdt_eval"] = gbdt_eval
+    if gbdt_params is not None and gbdt_params.sampled:
+        summary["gbdt_sampling"] = {"subsample": gbdt_params.subsample,
+                                    "colsample_bytree": gbdt_params.colsample_bytree, "seed": gbdt_params.seed}
     try:
         summary["registered_version"] = _track(s, model_type, res, summary, paths, Xte, names, say)
     except Exception as e:  # noqa: BLE001 - tracking is best effort (reference train_model.py:165-166)
@@ -260,16 +276,20 @@ class _Progress:
             os._exit(17)  # hard exit, like a killed rank: no cleanup, no flush
 
 
-def _job_signature(s, model_type, cv_folds, split_mode, cfg: dict, shape, comm) -> str:
+def _job_signature(s, model_type, cv_folds, split_mode, cfg: dict, shape, comm, gbdt_params=None) -> str:
     from .utils.checkpoint import config_signature
 
     st = os.stat(s.data_csv)
     return config_signature(data=os.path.abspath(s.data_csv), size=st.st_size, mtime=int(st.st_mtime),
                             shape=list(shape), model=model_type, folds=cv_folds, split=split_mode, cfg=cfg,
-                            world=1 if comm is None else comm.world_size)
+                            world=1 if comm is None else comm.world_size,
+                            # only when sampling is on: records written before it existed still match
+                            **({"gbdt_sampling": [gbdt_params.subsample, gbdt_params.colsample_bytree, gbdt_params.seed]}
+                               if gbdt_params is not None and gbdt_params.sampled else {}))
 
 
-def _cross_validate(model_type, cfg, folds, take, comm, mode: str, progress: _Progress | None = None) -> list:
+def _cross_validate(model_type, cfg, folds, take, comm, mode: str, progress: _Progress | None = None,
+                    gbdt_params=None) -> list:
     """K12 per-fold orchestration (train_model.py:58-85).  The table is resident (device split:
     on the GPU), so each fold is an on-device gather, never a host copy.
       dp   -- every fold is fitted data-parallel over all ranks (large folds);
@@ -281,7 +301,7 @@ def _cross_validate(model_type, cfg, folds, take, comm, mode: str, progress: _Pr
         for k, (ftr, fva) in enumerate(folds):
             if k in progress.folds:
                 continue
-            res = _fit(model_type, cfg, *take(_shard(ftr, comm)), comm)
+            res = _fit(model_type, cfg, *take(_shard(ftr, comm)), comm, gbdt_params=gbdt_params)
             progress.record(k, _score(model_type, res, *take(_shard(fva, comm)), comm))
         return [progress.folds[k] for k in range(len(folds))]
     if mode != "fold":
@@ -291,7 +311,7 @@ def _cross_validate(model_type, cfg, folds, take, comm, mode: str, progress: _Pr
         if k in progress.folds:
             continue
         ftr, fva = folds[k]
-        res = _fit(model_type, cfg, *take(ftr), None)
+        res = _fit(model_type, cfg, *take(ftr), None, gbdt_params=gbdt_params)
         mine[k] = _score(model_type, res, *take(fva), None)
     for part in comm.all_gather_object(mine):
         for k, auc in sorted(part.items()):
@@ -319,12 +339,12 @@ def _device_gbdt_cv_ok(model_type, cfg, dev, comm, progress) -> bool:
     return model_type == "gbdt" and dev.type == "cuda" and comm is None and not progress.folds and cfg.smote
 
 
-def _fit(model_type, cfg, X, y, comm=None, checkpoint: str | None = None):
+def _fit(model_type, cfg, X, y, comm=None, checkpoint: str | None = None, gbdt_params=None):
     if model_type == "logistic":
         return DevicePipeline(cfg, comm).fit(X, y)
     from .models.gbdt import GBDTPipeline
 
-    return GBDTPipeline(cfg, comm=comm, checkpoint_dir=checkpoint).fit(X, y)
+    return GBDTPipeline(cfg, params=gbdt_params, comm=comm, checkpoint_dir=checkpoint).fit(X, y)
 
 
 def _score(model_type, res, X, y, comm=None) -> float:
@@ -355,6 +375,8 @@ def _track(s: Settings, model_type, res, summary, paths, Xte, names, say):
         if summary["cv_auc_mean"] is not None:
             mlf.log_metric("cv_auc_mean", summary["cv_auc_mean"])
             mlf.log_metric("cv_auc_std", summary["cv_auc_std"])
+        for k, v in (summary.get("gbdt_sampling") or {}).items():
+            mlf.log_param(f"gbdt_{k}", v)
         ge = summary.get("gbdt_eval")
         if ge:
             mlf.log_param("gbdt_eval_metric", ",".join(ge["metrics"]))
@@ -405,6 +427,11 @@ def main(argv=None):
     ap.add_argument("--gbdt-early-stopping", type=int, default=None, metavar="N",
                     help="stop a fold after N rounds without improvement; the final fit grows "
                          "round(mean(best_iteration + 1)) trees")
+    ap.add_argument("--gbdt-subsample", type=float, default=1.0,
+                    help="row fraction every boosting round draws (stochastic boosting; 1.0: all rows)")
+    ap.add_argument("--gbdt-colsample-bytree", type=float, default=1.0,
+                    help="feature fraction every tree draws (1.0: all features)")
+    ap.add_argument("--gbdt-seed", type=int, default=0, help="seed of the row / feature draws")
     a = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO)
     comm = None
@@ -421,7 +448,8 @@ def main(argv=None):
         st = Settings.load(**over)
         out = run(st, model_type=a.model, cv_folds=a.cv_folds, model_dir=a.model_dir, comm=comm,
                   gbdt_eval_metric=a.gbdt_eval_metric.split(",") if a.gbdt_eval_metric else None,
-                  gbdt_early_stopping=a.gbdt_early_stopping)
+                  gbdt_early_stopping=a.gbdt_early_stopping, gbdt_subsample=a.gbdt_subsample,
+                  gbdt_colsample_bytree=a.gbdt_colsample_bytree, gbdt_seed=a.gbdt_seed)
     finally:
         if comm is not None:
             comm.close()

@@ -3,6 +3,7 @@
 credit_card-shaped synthetic rows after SMOTE, plus test AUC and inference rate.
 
     python tools/gbdt_bench.py [--rows 10000000] [--trees 100] [--json out.json]
+                               [--subsample 0.8] [--colsample-bytree 0.5] [--seed 0]
 """
 from __future__ import annotations
 
@@ -23,6 +24,9 @@ def main():
     ap.add_argument("--trees", type=int, default=100)
     ap.add_argument("--depth", type=int, default=5)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--subsample", type=float, default=1.0)
+    ap.add_argument("--colsample-bytree", type=float, default=1.0)
+    ap.add_argument("--seed", type=int, default=0)
     a = ap.parse_args()
     from fraud_detection_amd.data.synthetic import separable
     from fraud_detection_amd.models.gbdt import GBDTPipeline
@@ -33,8 +37,9 @@ def main():
     n_test = a.rows // 5
     X, y = separable(a.rows - n_test, seed=1000, device=dev)
     Xt, yt = separable(n_test, seed=5000, device=dev)
-    pipe = GBDTPipeline(TrainConfig(), gb.GBDTParams(n_estimators=a.trees, max_depth=a.depth))
-    GBDTPipeline(TrainConfig(), gb.GBDTParams(n_estimators=2, max_depth=a.depth)).fit(X, y)  # warm-up
+    sampling = dict(subsample=a.subsample, colsample_bytree=a.colsample_bytree, seed=a.seed)
+    pipe = GBDTPipeline(TrainConfig(), gb.GBDTParams(n_estimators=a.trees, max_depth=a.depth, **sampling))
+    GBDTPipeline(TrainConfig(), gb.GBDTParams(n_estimators=2, max_depth=a.depth, **sampling)).fit(X, y)  # warm-up
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     res = pipe.fit(X, y)
@@ -55,6 +60,8 @@ def main():
            "row_trees_per_s": round(res.n_train_rows * a.trees / res.timings["boost"], 1),
            "auc": round(ev["auc"], 6), "predict_rows_per_s": round(n_test / pred_s, 1),
            "scale_pos_weight": round(res.scale_pos_weight, 3)}
+    if pipe.params.sampled:
+        out.update(sampling)
     print(json.dumps(out))
     if a.json:
         with open(a.json, "w") as f:
