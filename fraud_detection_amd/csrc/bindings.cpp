@@ -1001,6 +1001,48 @@ PYBIND11_MODULE(_fdx_native, m) {
                                P<const float>(leaf), depth, P<float>(margin), P<const uint8_t>(label),
                                P<long long>(rec), S(s));
   });
+  m.def("gbdt_grad_weighted", [](u margin, u label, u weight, int64_t n, float spw, float gscale, float hscale, u gh,
+                                 u s) {
+    fdx::launch_gbdt_grad_weighted(P<const float>(margin), P<const uint8_t>(label), P<const float>(weight), n, spw,
+                                   gscale, hscale, P<uint32_t>(gh), S(s));
+  });
+  m.def("gbdt_grad_sampled_weighted", [](u margin, u label, u weight, int64_t n, float spw, float gscale, float hscale,
+                                         u gh, uint64_t seed, int64_t round, int64_t row_offset, uint32_t threshold,
+                                         u s) {
+    fdx::launch_gbdt_grad_sampled_weighted(P<const float>(margin), P<const uint8_t>(label), P<const float>(weight), n,
+                                           spw, gscale, hscale, P<uint32_t>(gh), seed, round, row_offset, threshold,
+                                           S(s));
+  });
+  m.def("gbdt_margin_weighted", [](u binsT, int64_t ldt, int64_t n, u feat, u bin, u leaf, int depth, u margin,
+                                   u label, u weight, float spw, float gscale, float hscale, u gh, u s) {
+    fdx::launch_gbdt_margin_weighted(P<const uint8_t>(binsT), ldt, n, P<const int>(feat), P<const int>(bin),
+                                     P<const float>(leaf), depth, P<float>(margin), P<const uint8_t>(label),
+                                     P<const float>(weight), spw, gscale, hscale, P<uint32_t>(gh), S(s));
+  });
+  m.def("gbdt_margin_sampled_weighted", [](u binsT, int64_t ldt, int64_t n, u feat, u bin, u leaf, int depth,
+                                           u margin, u label, u weight, float spw, float gscale, float hscale, u gh,
+                                           uint64_t seed, int64_t round, int64_t row_offset, uint32_t threshold,
+                                           u s) {
+    fdx::launch_gbdt_margin_sampled_weighted(P<const uint8_t>(binsT), ldt, n, P<const int>(feat), P<const int>(bin),
+                                             P<const float>(leaf), depth, P<float>(margin), P<const uint8_t>(label),
+                                             P<const float>(weight), spw, gscale, hscale, P<uint32_t>(gh), seed,
+                                             round, row_offset, threshold, S(s));
+  });
+  m.def("gbdt_weight_stats", [](u weight, u label, int64_t n_table, int64_t hole_at, int64_t hole_len, float spw,
+                                u out, u s) {
+    fdx::launch_gbdt_weight_stats(P<const float>(weight), P<const uint8_t>(label), n_table, hole_at, hole_len, spw,
+                                  P<unsigned long long>(out), S(s));
+  });
+  m.def("gbdt_eval_weighted", [](u margin, u label, u weight, double wscale, int64_t r0, int64_t r1, u rec, u s) {
+    fdx::launch_gbdt_eval_weighted(P<const float>(margin), P<const uint8_t>(label), P<const float>(weight), wscale, r0,
+                                   r1, P<long long>(rec), S(s));
+  });
+  m.def("gbdt_eval_walk_weighted", [](u binsT, int64_t ldt, int64_t n, u feat, u bin, u leaf, int depth, u margin,
+                                      u label, u weight, double wscale, u rec, u s) {
+    fdx::launch_gbdt_eval_walk_weighted(P<const uint8_t>(binsT), ldt, n, P<const int>(feat), P<const int>(bin),
+                                        P<const float>(leaf), depth, P<float>(margin), P<const uint8_t>(label),
+                                        P<const float>(weight), wscale, P<long long>(rec), S(s));
+  });
   m.def("gbdt_predict", [](u X, int64_t n, int ld, int d, u feat, u thr, u leaf, int ntrees, int depth, float base,
                            u out, u s) {
     fdx::launch_gbdt_predict(P<const float>(X), n, ld, d, P<const int>(feat), P<const float>(thr), P<const float>(leaf),

@@ -25,6 +25,9 @@
 //    contraction disabled (the numpy oracle in ops/reference.py reproduces it bit-for-bit).
 //  * No host synchronisation inside a fit: segment sizes, build flags and leaf values stay on
 //    device, so a boosting round is a fixed launch sequence (hipGraph-capturable).
+#include <cmath>
+#include <type_traits>
+
 #include "common.h"
 #include "launchers.h"
 
@@ -160,10 +163,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void g
 __device__ __forceinline__ uint32_t pack_gh(int2 q) {
   return (uint32_t)(uint16_t)(int16_t)q.x | ((uint32_t)(uint16_t)q.y << 16);
 }
-__device__ __forceinline__ int2 quantised_grad(float margin, bool pos, float spw, float gscale, float hscale) {
+// `wrow`: the row's sample weight, one more exact factor in front of the quantisation (an fp32 times
+// an fp32 is exact in fp64).  Every variant calls this one function, the unweighted ones with the
+// constant 1.0, which the compiler folds away (x * 1.0 == x for every x): their code is what it was,
+// and a weighted row with w = 1 gets the unweighted word bit for bit.
+__device__ __forceinline__ int2 quantised_grad(float margin, bool pos, float spw, float gscale, float hscale,
+                                               double wrow = 1.0) {
   const double m = (double)margin;
   const double p = 1.0 / (1.0 + exp(-m));
-  const double w = pos ? (double)spw : 1.0;
+  const double w = wrow * (pos ? (double)spw : 1.0);
   const double g = (p - (pos ? 1.0 : 0.0)) * w;
   const double h = fmax(p * (1.0 - p), 1e-16) * w;
   return make_int2((int)rint(g * (double)gscale), (int)rint(h * (double)hscale));
@@ -192,20 +200,76 @@ __device__ __forceinline__ bool row_in_sample(int64_t r, const RowSample& s) {
   return w < s.thresh;
 }
 
+// Trailing argument pack of the gradient-writing kernels: [const float* weight][, RowSample].  The
+// pack's types tell the variants apart, so the instantiations without weights keep their names,
+// arguments and code.  weight: float32 [n] per-row sample weights (finite, >= 0; the fit checks).
+template <bool SAMPLE, typename... RS>
+constexpr bool kTailWeighted = sizeof...(RS) == (SAMPLE ? 2 : 1);
+__device__ __forceinline__ const float* tail_weight(const float* w) { return w; }
+__device__ __forceinline__ const float* tail_weight(const float* w, const RowSample&) { return w; }
+__device__ __forceinline__ const RowSample& tail_sample(const RowSample& s) { return s; }
+__device__ __forceinline__ const RowSample& tail_sample(const float*, const RowSample& s) { return s; }
+
 // First round of a fit only: later rounds get their gradients from gbdt_margin_kernel<true>.
-// RS is empty without SAMPLE -- the unsampled kernel keeps its arguments -- and one RowSample with it.
+// RS is empty without SAMPLE and without weights -- that kernel keeps its arguments -- and holds the
+// weight pointer and / or one RowSample otherwise.  The sample test comes first: an out-of-sample
+// row loads neither its margin nor its weight.
 template <bool SAMPLE = false, typename... RS>
 __global__ __launch_bounds__(256) void gbdt_grad_kernel(const float* __restrict__ margin,
                                                         const uint8_t* __restrict__ label, int64_t n,
                                                         float spw, float gscale, float hscale,
                                                         uint32_t* __restrict__ gh, RS... rs) {
-  static_assert(sizeof...(RS) == (SAMPLE ? 1 : 0), "a RowSample goes with SAMPLE, and only with it");
+  constexpr bool WEIGHT = kTailWeighted<SAMPLE, RS...>;
+  static_assert(sizeof...(RS) == (SAMPLE ? 1 : 0) + (WEIGHT ? 1 : 0), "tail: [weight][, RowSample with SAMPLE]");
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     if constexpr (SAMPLE) {
-      if (!row_in_sample(i, rs...)) { gh[i] = 0u; continue; }
+      if (!row_in_sample(i, tail_sample(rs...))) { gh[i] = 0u; continue; }
     }
-    gh[i] = pack_gh(quantised_grad(margin[i], label[i] != 0, spw, gscale, hscale));
+    if constexpr (WEIGHT) {
+      gh[i] = pack_gh(quantised_grad(margin[i], label[i] != 0, spw, gscale, hscale, (double)tail_weight(rs...)[i]));
+    } else {
+      gh[i] = pack_gh(quantised_grad(margin[i], label[i] != 0, spw, gscale, hscale));
+    }
+  }
+}
+
+// One pass over a fit's weights (float32, one per TABLE row, the block [hole_at, hole_at + hole_len)
+// left out): what the fit validates and scales by, read by the host once.
+//   out[0] = max over the rows of the weight's bits (non-negative floats order like their bits),
+//   out[1] = min over the rows with w > 0 of the bits of the fp64 w_eff = w * (label ? spw : 1)
+//            (label null: w_eff = w); the caller presets it to +inf's bits,
+//   out[2] = rows whose weight is NaN, infinite or negative (they enter neither of the above).
+// A thread folds its rows, a wave meets by xor shuffles and lane 0 issues three 64-bit atomics.
+__global__ __launch_bounds__(256) void gbdt_weight_stats_kernel(const float* __restrict__ weight,
+                                                                const uint8_t* __restrict__ label, int64_t n_fit,
+                                                                int64_t hole_at, int64_t hole_len, float spw,
+                                                                unsigned long long* __restrict__ out) {
+  unsigned long long wmax = 0ull, effmin = 0x7FF0000000000000ull, bad = 0ull;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n_fit; p += stride) {
+    const int64_t r = hole_row(p, hole_at, hole_len);
+    const float w = weight[r];
+    if (!(w >= 0.0f) || w > 3.402823466e+38f) { bad += 1; continue; }
+    if (w > 0.0f) {  // (-0.0 is a zero weight, whatever its bits)
+      const unsigned long long wb = (unsigned long long)__float_as_uint(w);
+      wmax = wb > wmax ? wb : wmax;
+      const double eff = (double)w * ((label != nullptr && label[r] != 0) ? (double)spw : 1.0);
+      const unsigned long long eb = (unsigned long long)__double_as_longlong(eff);
+      effmin = eb < effmin ? eb : effmin;
+    }
+  }
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) {
+    const unsigned long long a = __shfl_xor(wmax, off, kWave), b = __shfl_xor(effmin, off, kWave);
+    wmax = a > wmax ? a : wmax;
+    effmin = b < effmin ? b : effmin;
+  }
+  bad = wave_sum(bad);
+  if (lane_id() == 0) {
+    atomicMax(out, wmax);
+    atomicMin(out + 1, effmin);
+    if (bad) atomicAdd(out + 2, bad);
   }
 }
 
@@ -1124,7 +1188,10 @@ __global__ void gbdt_leaf_kernel(const long long* __restrict__ ng, const long lo
 // over a depth-5 walk -- so walking 4 rows per thread in lockstep measured slower (68-71 us).
 // SAMPLE (with GRAD): the next round's row sample -- an out-of-sample row gets the word 0 and skips
 // the fp64 sigmoid; its margin is updated like every other row's.  RS as in gbdt_grad_kernel: empty
-// without SAMPLE, so the unsampled instantiations keep their arguments.
+// without SAMPLE and without weights, so those instantiations keep their arguments.
+// With weights (GRAD only) the row's sample test and then its 4-byte weight load are issued BEFORE
+// the walk: the load depends on nothing the walk produces, so it is in flight under the walk's
+// dependent bin reads and adds no latency behind them, and an out-of-sample row loads no weight.
 template <bool GRAD, bool SAMPLE = false, typename... RS>
 __global__ __launch_bounds__(256) void gbdt_margin_kernel(const uint8_t* __restrict__ binsT, int64_t ldt,
                                                           int64_t n, const int* __restrict__ feat,
@@ -1134,7 +1201,9 @@ __global__ __launch_bounds__(256) void gbdt_margin_kernel(const uint8_t* __restr
                                                           const uint8_t* __restrict__ label, float spw,
                                                           float gscale, float hscale, uint32_t* __restrict__ gh,
                                                           RS... rs) {
-  static_assert(sizeof...(RS) == (SAMPLE ? 1 : 0) && (GRAD || !SAMPLE), "a RowSample goes with GRAD and SAMPLE only");
+  constexpr bool WEIGHT = kTailWeighted<SAMPLE, RS...>;
+  static_assert(sizeof...(RS) == (SAMPLE ? 1 : 0) + (WEIGHT ? 1 : 0) && (GRAD || sizeof...(RS) == 0),
+                "tail: [weight][, RowSample with SAMPLE], with GRAD only");
   __shared__ int sf[kGBMaxNodes], sb[kGBMaxNodes];
   __shared__ float sl[kGBMaxNodes + 1];
   const int ni = heap_first(depth);
@@ -1146,14 +1215,25 @@ __global__ __launch_bounds__(256) void gbdt_margin_kernel(const uint8_t* __restr
   __syncthreads();
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += stride) {
+    [[maybe_unused]] bool in_sample = true;
+    [[maybe_unused]] float w = 0.0f;
+    if constexpr (WEIGHT) {
+      if constexpr (SAMPLE) in_sample = row_in_sample(r, tail_sample(rs...));
+      if (in_sample) w = tail_weight(rs...)[r];
+    }
     int node = 0;
     for (int l = 0; l < depth; ++l) node = 2 * node + 1 + (int)goes_right(binsT, ldt, r, node, sf, sb);
     const float m = margin[r] + sl[node - ni];
     margin[r] = m;
-    if constexpr (GRAD && SAMPLE) {
-      if (!row_in_sample(r, rs...)) { gh[r] = 0u; continue; }
+    if constexpr (WEIGHT) {
+      if (!in_sample) { gh[r] = 0u; continue; }
+      gh[r] = pack_gh(quantised_grad(m, label[r] != 0, spw, gscale, hscale, (double)w));
+    } else {
+      if constexpr (GRAD && SAMPLE) {
+        if (!row_in_sample(r, rs...)) { gh[r] = 0u; continue; }
+      }
+      if constexpr (GRAD) gh[r] = pack_gh(quantised_grad(m, label[r] != 0, spw, gscale, hscale));
     }
-    if constexpr (GRAD) gh[r] = pack_gh(quantised_grad(m, label[r] != 0, spw, gscale, hscale));
   }
 }
 
@@ -1183,18 +1263,40 @@ constexpr int64_t kEvalMaxRows = (int64_t)1 << 27;
 constexpr double kEvalLossCap = 36.841361487904734;  // -ln(1e-16)
 constexpr double kEvalLossScale = 1073741824.0;      // 2^30
 
-__device__ __forceinline__ long long eval_loss_q(float margin, bool pos) {
+__device__ __forceinline__ double eval_loss(float margin, bool pos) {
   const double m = (double)margin;
   const double z = pos ? -m : m;
   const double sp = fmax(z, 0.0) + log1p(exp(-fabs(z)));
-  return (long long)rint(fmin(sp, kEvalLossCap) * kEvalLossScale);
+  return fmin(sp, kEvalLossCap);
+}
+__device__ __forceinline__ long long eval_loss_q(float margin, bool pos) {
+  return (long long)rint(eval_loss(margin, pos) * kEvalLossScale);
 }
 
-template <bool WALK>
+// Weighted records (xgboost's sample_weight_eval_set; reference_gbdt.eval_record_weighted): the
+// trailing pack EW holds an EvalWeight, the kernel without weights keeps its arguments and code.
+// With u = w * wscale <= 2^16 (wscale a power of two: exact), a row adds
+// rint(min(softplus, cap) * u * 2^14) to loss_q and, when it is an error row, rint(u * 2^14) to the
+// error column; n_pos and n_rows stay counts.  u = 2^16 (all weights equal) gives the unweighted
+// loss term bit for bit.  A row's loss term stays below 36.85 * 2^30, so the 2^27-row bound holds.
+// The weights are indexed by the row like margin and label (the hole form: by TABLE row).
+struct EvalWeight {
+  const float* w;
+  double wscale;  // 2^floor(log2(2^16 / max weight))
+};
+constexpr double kEvalWeightScale = 16384.0;  // 2^14
+__device__ __forceinline__ const EvalWeight& eval_weight(const EvalWeight& e) { return e; }
+__device__ __forceinline__ long long eval_loss_q(float margin, bool pos, double u) {
+  return (long long)rint(eval_loss(margin, pos) * u * kEvalWeightScale);
+}
+
+template <bool WALK, typename... EW>
 __global__ __launch_bounds__(kEvalThreads) void gbdt_eval_kernel(
     float* __restrict__ margin, const uint8_t* __restrict__ label, int64_t r0, int64_t r1,
     const uint8_t* __restrict__ binsT, int64_t ldt, const int* __restrict__ feat, const int* __restrict__ bin,
-    const float* __restrict__ leaf, int depth, unsigned long long* __restrict__ rec) {
+    const float* __restrict__ leaf, int depth, unsigned long long* __restrict__ rec, EW... ew) {
+  constexpr bool WEIGHT = sizeof...(EW) == 1;
+  static_assert(sizeof...(EW) <= 1, "at most one EvalWeight");
   __shared__ int sf[kGBMaxNodes], sb[kGBMaxNodes];
   __shared__ float sl[kGBMaxNodes + 1];
   __shared__ long long red[kEvalThreads / kWave][4];
@@ -1208,10 +1310,14 @@ __global__ __launch_bounds__(kEvalThreads) void gbdt_eval_kernel(
     __syncthreads();
   }
   long long loss = 0;
-  int err = 0, npos = 0, rows = 0;  // <= 2^27 rows in all: a thread's counts fit an int
+  // <= 2^27 rows in all: a thread's counts fit an int; a weighted error term is up to 2^30 a row
+  std::conditional_t<WEIGHT, long long, int> err = 0;
+  int npos = 0, rows = 0;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t r = r0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < r1; r += stride) {
     float m = margin[r];
+    [[maybe_unused]] double u = 0.0;  // loaded ahead of the walk, which does not depend on it
+    if constexpr (WEIGHT) u = (double)eval_weight(ew...).w[r] * eval_weight(ew...).wscale;
     if constexpr (WALK) {
       int node = 0;
       for (int l = 0; l < depth; ++l) node = 2 * node + 1 + (int)goes_right(binsT, ldt, r, node, sf, sb);
@@ -1219,8 +1325,13 @@ __global__ __launch_bounds__(kEvalThreads) void gbdt_eval_kernel(
       margin[r] = m;
     }
     const bool pos = label[r] != 0;
-    loss += eval_loss_q(m, pos);
-    err += (int)((m > 0.0f) != pos);
+    if constexpr (WEIGHT) {
+      loss += eval_loss_q(m, pos, u);
+      if ((m > 0.0f) != pos) err += (long long)rint(u * kEvalWeightScale);
+    } else {
+      loss += eval_loss_q(m, pos);
+      err += (int)((m > 0.0f) != pos);
+    }
     npos += (int)pos;
     rows += 1;
   }
@@ -1325,6 +1436,37 @@ void launch_gbdt_grad_sampled(const float* margin, const uint8_t* label, int64_t
   const int grid = stream_grid(n, 256, 4096);
   gbdt_grad_kernel<true, RowSample><<<grid, 256, 0, stream>>>(margin, label, n, spw, gscale, hscale, gh, rs);
   check_launch("gbdt_grad_sampled");
+}
+
+void launch_gbdt_grad_weighted(const float* margin, const uint8_t* label, const float* weight, int64_t n, float spw,
+                               float gscale, float hscale, uint32_t* gh, hipStream_t stream) {
+  if (!weight) throw std::runtime_error("gbdt_grad_weighted: null weight pointer");
+  const int grid = stream_grid(n, 256, 4096);
+  gbdt_grad_kernel<false, const float*><<<grid, 256, 0, stream>>>(margin, label, n, spw, gscale, hscale, gh, weight);
+  check_launch("gbdt_grad_weighted");
+}
+
+void launch_gbdt_grad_sampled_weighted(const float* margin, const uint8_t* label, const float* weight, int64_t n,
+                                       float spw, float gscale, float hscale, uint32_t* gh, uint64_t seed,
+                                       int64_t round, int64_t row_offset, uint32_t threshold, hipStream_t stream) {
+  if (!weight) throw std::runtime_error("gbdt_grad_sampled_weighted: null weight pointer");
+  const RowSample rs = row_sample(seed, round, row_offset, n, threshold, "gbdt_grad_sampled_weighted");
+  const int grid = stream_grid(n, 256, 4096);
+  gbdt_grad_kernel<true, const float*, RowSample><<<grid, 256, 0, stream>>>(margin, label, n, spw, gscale, hscale, gh,
+                                                                            weight, rs);
+  check_launch("gbdt_grad_sampled_weighted");
+}
+
+void launch_gbdt_weight_stats(const float* weight, const uint8_t* label, int64_t n_table, int64_t hole_at,
+                              int64_t hole_len, float spw, unsigned long long* out, hipStream_t stream) {
+  if (!weight || !out) throw std::runtime_error("gbdt_weight_stats: null pointer");
+  if (hole_at < 0 || hole_len < 0 || hole_at > n_table - hole_len)
+    throw std::runtime_error("gbdt_weight_stats: hole outside the table rows");
+  const int64_t n_fit = n_table - hole_len;
+  if (n_fit == 0) return;
+  gbdt_weight_stats_kernel<<<stream_grid(n_fit, 256 * 4, 1024), 256, 0, stream>>>(weight, label, n_fit, hole_at,
+                                                                                 hole_len, spw, out);
+  check_launch("gbdt_weight_stats");
 }
 
 int gbdt_hist_blocks() {
@@ -1478,9 +1620,37 @@ void launch_gbdt_margin_sampled(const uint8_t* binsT, int64_t ldt, int64_t n, co
   check_launch("gbdt_margin_sampled");
 }
 
-template <bool WALK>
+void launch_gbdt_margin_weighted(const uint8_t* binsT, int64_t ldt, int64_t n, const int* feat, const int* bin,
+                                 const float* leaf, int depth, float* margin, const uint8_t* label,
+                                 const float* weight, float spw, float gscale, float hscale, uint32_t* gh,
+                                 hipStream_t stream) {
+  if (depth < 1 || depth > 7) throw std::runtime_error("gbdt_margin_weighted: depth must be in [1, 7]");
+  if (!gh) throw std::runtime_error("gbdt_margin_weighted: the weights apply to the gradients, gh is required");
+  if (!weight) throw std::runtime_error("gbdt_margin_weighted: null weight pointer");
+  const int grid = stream_grid(n, 256, 4096);
+  gbdt_margin_kernel<true, false, const float*><<<grid, 256, 0, stream>>>(binsT, ldt, n, feat, bin, leaf, depth, margin,
+                                                                          label, spw, gscale, hscale, gh, weight);
+  check_launch("gbdt_margin_weighted");
+}
+
+void launch_gbdt_margin_sampled_weighted(const uint8_t* binsT, int64_t ldt, int64_t n, const int* feat, const int* bin,
+                                         const float* leaf, int depth, float* margin, const uint8_t* label,
+                                         const float* weight, float spw, float gscale, float hscale, uint32_t* gh,
+                                         uint64_t seed, int64_t round, int64_t row_offset, uint32_t threshold,
+                                         hipStream_t stream) {
+  if (depth < 1 || depth > 7) throw std::runtime_error("gbdt_margin_sampled_weighted: depth must be in [1, 7]");
+  if (!gh) throw std::runtime_error("gbdt_margin_sampled_weighted: the sample applies to the gradients, gh is required");
+  if (!weight) throw std::runtime_error("gbdt_margin_sampled_weighted: null weight pointer");
+  const RowSample rs = row_sample(seed, round, row_offset, n, threshold, "gbdt_margin_sampled_weighted");
+  const int grid = stream_grid(n, 256, 4096);
+  gbdt_margin_kernel<true, true, const float*, RowSample><<<grid, 256, 0, stream>>>(
+      binsT, ldt, n, feat, bin, leaf, depth, margin, label, spw, gscale, hscale, gh, weight, rs);
+  check_launch("gbdt_margin_sampled_weighted");
+}
+
+template <bool WALK, typename... EW>
 static int gbdt_eval_grid(int64_t rows) {
-  static const int resident = resident_cap(gbdt_eval_kernel<WALK>, kEvalThreads);
+  static const int resident = resident_cap(gbdt_eval_kernel<WALK, EW...>, kEvalThreads);
   static const int cap = resident < kEvalBlocksPerCU * device_cu_count() ? resident : kEvalBlocksPerCU * device_cu_count();
   return capped_grid(rows, kEvalThreads * kEvalRowsPerThread, cap);
 }
@@ -1506,6 +1676,37 @@ void launch_gbdt_eval_walk(const uint8_t* binsT, int64_t ldt, int64_t n, const i
   gbdt_eval_kernel<true><<<gbdt_eval_grid<true>(n), kEvalThreads, 0, stream>>>(
       margin, label, 0, n, binsT, ldt, feat, bin, leaf, depth, reinterpret_cast<unsigned long long*>(rec));
   check_launch("gbdt_eval_walk");
+}
+
+static EvalWeight eval_weight_arg(const float* weight, double wscale, const char* what) {
+  if (!weight) throw std::runtime_error(std::string(what) + ": null weight pointer");
+  if (!(wscale > 0.0) || !std::isfinite(wscale)) throw std::runtime_error(std::string(what) + ": bad weight scale");
+  return EvalWeight{weight, wscale};
+}
+
+void launch_gbdt_eval_weighted(const float* margin, const uint8_t* label, const float* weight, double wscale,
+                               int64_t r0, int64_t r1, long long* rec, hipStream_t stream) {
+  if (r0 < 0 || r1 < r0) throw std::runtime_error("gbdt_eval_weighted: bad row range");
+  if (r1 - r0 > kEvalMaxRows) throw std::runtime_error("gbdt_eval_weighted: at most 2^27 eval rows (int64 loss sum)");
+  const EvalWeight ew = eval_weight_arg(weight, wscale, "gbdt_eval_weighted");
+  if (r1 == r0) return;
+  gbdt_eval_kernel<false, EvalWeight><<<gbdt_eval_grid<false, EvalWeight>(r1 - r0), kEvalThreads, 0, stream>>>(
+      const_cast<float*>(margin), label, r0, r1, nullptr, 0, nullptr, nullptr, nullptr, 0,
+      reinterpret_cast<unsigned long long*>(rec), ew);
+  check_launch("gbdt_eval_weighted");
+}
+
+void launch_gbdt_eval_walk_weighted(const uint8_t* binsT, int64_t ldt, int64_t n, const int* feat, const int* bin,
+                                    const float* leaf, int depth, float* margin, const uint8_t* label,
+                                    const float* weight, double wscale, long long* rec, hipStream_t stream) {
+  if (depth < 1 || depth > 7) throw std::runtime_error("gbdt_eval_walk_weighted: depth must be in [1, 7]");
+  if (n < 0 || n > ldt) throw std::runtime_error("gbdt_eval_walk_weighted: rows exceed the bins' leading dimension");
+  if (n > kEvalMaxRows) throw std::runtime_error("gbdt_eval_walk_weighted: at most 2^27 eval rows (int64 loss sum)");
+  const EvalWeight ew = eval_weight_arg(weight, wscale, "gbdt_eval_walk_weighted");
+  if (n == 0) return;
+  gbdt_eval_kernel<true, EvalWeight><<<gbdt_eval_grid<true, EvalWeight>(n), kEvalThreads, 0, stream>>>(
+      margin, label, 0, n, binsT, ldt, feat, bin, leaf, depth, reinterpret_cast<unsigned long long*>(rec), ew);
+  check_launch("gbdt_eval_walk_weighted");
 }
 
 void launch_gbdt_predict(const float* X, int64_t n, int ld, int d, const int* feat, const float* thr,

@@ -496,5 +496,37 @@ void launch_gbdt_eval_walk(const uint8_t* binsT, int64_t ldt, int64_t n, const i
 void launch_gbdt_predict(const float* X, int64_t n, int ld, int d, const int* feat, const float* thr,
                          const float* leaf, int ntrees, int depth, float base_margin, float* out,
                          hipStream_t stream);
+// Per-row sample weights (float32 [n], finite and >= 0, one per table row): the weighted forms of
+// the gradient-writing kernels.  A row's (g, h) take the factor w in fp64 before the quantisation
+// (reference_gbdt.gradients); w = 1 gives the unweighted word bit for bit, w = 0 the word 0.  The
+// sample test of the sampled forms comes first.  A null weight pointer is refused.
+void launch_gbdt_grad_weighted(const float* margin, const uint8_t* label, const float* weight, int64_t n, float spw,
+                               float gscale, float hscale, uint32_t* gh, hipStream_t stream);
+void launch_gbdt_grad_sampled_weighted(const float* margin, const uint8_t* label, const float* weight, int64_t n,
+                                       float spw, float gscale, float hscale, uint32_t* gh, uint64_t seed,
+                                       int64_t round, int64_t row_offset, uint32_t threshold, hipStream_t stream);
+void launch_gbdt_margin_weighted(const uint8_t* binsT, int64_t ldt, int64_t n, const int* feat, const int* bin,
+                                 const float* leaf, int depth, float* margin, const uint8_t* label,
+                                 const float* weight, float spw, float gscale, float hscale, uint32_t* gh,
+                                 hipStream_t stream);
+void launch_gbdt_margin_sampled_weighted(const uint8_t* binsT, int64_t ldt, int64_t n, const int* feat, const int* bin,
+                                         const float* leaf, int depth, float* margin, const uint8_t* label,
+                                         const float* weight, float spw, float gscale, float hscale, uint32_t* gh,
+                                         uint64_t seed, int64_t round, int64_t row_offset, uint32_t threshold,
+                                         hipStream_t stream);
+// One reduction over a fit's weights (the table's rows minus the hole), ATOMICALLY merged into
+// out = uint64 [3] preset to (0, bits of +inf as fp64, 0): the largest weight's fp32 bits, the
+// fp64 bits of the smallest positive w * (label ? spw : 1) (label null: w), and the count of NaN,
+// infinite or negative weights.
+void launch_gbdt_weight_stats(const float* weight, const uint8_t* label, int64_t n_table, int64_t hole_at,
+                              int64_t hole_len, float spw, unsigned long long* out, hipStream_t stream);
+// Weighted validation records (reference_gbdt.eval_record_weighted): u = weight * wscale <= 2^16,
+// loss_q += rint(loss * u * 2^14), error column += rint(u * 2^14) per error row; n_pos, n_rows
+// counts.  `weight` is indexed by the row like margin and label (gbdt_eval: rows [r0, r1)).
+void launch_gbdt_eval_weighted(const float* margin, const uint8_t* label, const float* weight, double wscale,
+                               int64_t r0, int64_t r1, long long* rec, hipStream_t stream);
+void launch_gbdt_eval_walk_weighted(const uint8_t* binsT, int64_t ldt, int64_t n, const int* feat, const int* bin,
+                                    const float* leaf, int depth, float* margin, const uint8_t* label,
+                                    const float* weight, double wscale, long long* rec, hipStream_t stream);
 
 }  // namespace fdx

@@ -97,23 +97,48 @@ class GBDTClassifier:
             st.setdefault(k, None)
         self.__dict__.update(st)
 
-    def fit(self, X, y, comm=None, eval_set=None, verbose: bool = False):
+    def fit(self, X, y, sample_weight=None, comm=None, eval_set=None, verbose: bool = False,
+            sample_weight_eval_set=None):
         """``eval_set``: ``[(Xv, yv)]`` (exactly one set, xgboost's list form) evaluated after every
         round with the constructor's ``eval_metric`` (a name or a list of "logloss", "error", "auc",
         "aucpr"; default "logloss"; "aucpr" is sklearn's average precision over tie groups, which
         xgboost's ``aucpr`` interpolates slightly differently); with
         ``early_stopping_rounds`` the last metric stops the fit and the model keeps trees
         [: best_iteration + 1] (xgboost keeps the tail and never predicts with it).  Without
-        ``eval_set`` nothing is evaluated."""
+        ``eval_set`` nothing is evaluated.
+
+        ``sample_weight``: one weight per row of X (numpy or torch; finite, >= 0, at least one
+        positive), multiplied into the row's gradient pair together with ``scale_pos_weight``
+        (ops/gbdt.fit_binned has the definitions and the 14-bit resolution limit).
+        ``sample_weight_eval_set``: a list with one array, the eval rows' weights, as in xgboost;
+        "logloss" and "error" become weighted means, "auc" / "aucpr" with evaluation weights raise
+        NotImplementedError.  ``None`` everywhere is the unweighted call.  Out of scope: the quantile
+        cuts stay unweighted, and GBDTPipeline, DeviceGBDTCV and the train entry point take no
+        weights (SMOTE's synthetic rows have no defined weight; imblearn drops weights too)."""
         dev = self._dev(X)
         Xt = _as_tensor(X, dev)
         yt = (y if isinstance(y, torch.Tensor) else torch.from_numpy(np.asarray(y))).to(dev).to(torch.uint8)
+
+        def weights(w):
+            if w is None:
+                return None
+            w = w if isinstance(w, torch.Tensor) else torch.from_numpy(np.asarray(w))
+            return w.reshape(-1).to(dev).to(torch.float32).contiguous()
+
+        if sample_weight_eval_set is not None:
+            if eval_set is None:
+                raise ValueError("sample_weight_eval_set needs an eval_set")
+            if isinstance(sample_weight_eval_set, (list, tuple)):
+                if len(sample_weight_eval_set) != 1:
+                    raise ValueError("sample_weight_eval_set takes exactly one array (one eval set is supported)")
+                sample_weight_eval_set = sample_weight_eval_set[0]
+        kw = dict(comm=comm, sample_weight=weights(sample_weight))
         self._dens = None
         self.evals_result_, self.best_iteration, self.best_score = None, None, None
         if eval_set is None:
             if self.early_stopping_rounds is not None:
                 raise ValueError("early_stopping_rounds needs fit(..., eval_set=[(Xv, yv)])")
-            self.ensemble = gb.fit(Xt, yt.contiguous(), self.params, comm=comm)
+            self.ensemble = gb.fit(Xt, yt.contiguous(), self.params, **kw)
             return self
         if isinstance(eval_set, tuple):
             eval_set = [eval_set]
@@ -123,8 +148,9 @@ class GBDTClassifier:
         Xv = _as_tensor(Xv, dev)
         yv = (yv if isinstance(yv, torch.Tensor) else torch.from_numpy(np.asarray(yv))).to(dev).to(torch.uint8)
         metrics = self.eval_metric if self.eval_metric is not None else "logloss"
-        self.ensemble, rec = gb.fit(Xt, yt.contiguous(), self.params, comm=comm, eval_set=(Xv, yv.contiguous()),
-                                    eval_metric=metrics, early_stopping_rounds=self.early_stopping_rounds)
+        self.ensemble, rec = gb.fit(Xt, yt.contiguous(), self.params, eval_set=(Xv, yv.contiguous()),
+                                    eval_metric=metrics, early_stopping_rounds=self.early_stopping_rounds,
+                                    eval_sample_weight=weights(sample_weight_eval_set), **kw)
         self.evals_result_ = {"validation_0": {k: list(v) for k, v in rec.history.items()}}
         self.best_iteration, self.best_score = rec.best_iteration, rec.best_score
         if verbose:

@@ -8,6 +8,7 @@ update.  Nothing in a round synchronises with the host.  CPU tensors run the num
 from __future__ import annotations
 
 import os
+import warnings
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -234,7 +235,11 @@ class EvalRecord:
     them (logloss = loss_q / 2^30 / n_rows, error = n_err / n_rows) and ``twice_pairs`` the AUC's
     exact pair counts (auc = twice_pairs / (2 P N)), ``ap_q`` the average precision's exact integer
     sums (aucpr = ap_q / 2^30 / P, NaN without positives).  ``best_iteration`` is the first round
-    with the best value of the LAST metric, ``best_score`` that value."""
+    with the best value of the LAST metric, ``best_score`` that value.
+
+    With evaluation weights (``eval_sample_weight``) ``weight_q`` is the eval set's exact weight sum
+    wsum_q and the records are reference_gbdt.eval_record_weighted's (loss_q, err_q, n_pos, n_rows):
+    logloss = loss_q / weight_q, error = err_q / weight_q.  Without them it is None."""
     history: dict
     best_iteration: int
     best_score: float
@@ -243,6 +248,7 @@ class EvalRecord:
     twice_pairs: np.ndarray | None = None
     stopped: bool = False
     ap_q: np.ndarray | None = None
+    weight_q: int | None = None
 
     @property
     def n_rounds(self) -> int:
@@ -274,6 +280,7 @@ class _Eval:
 
     def __init__(self, metrics, patience, T):
         self.metrics, self.patience, self.T = metrics, patience, T
+        self.weight_q = None   # the eval set's weight sum wsum_q under evaluation weights
         self.records = np.zeros((T, 4), np.int64)
         self.twice = np.zeros(T, np.int64)
         self.apq = np.zeros(T, np.int64)
@@ -322,7 +329,9 @@ class _Eval:
         N = rec[:, 3].astype(np.float64) - P
         hist = {}
         for name in self.metrics:
-            if name == "logloss":
+            if name in ("logloss", "error") and self.weight_q is not None:
+                v = rec[:, 0 if name == "logloss" else 1].astype(np.float64) / float(self.weight_q)
+            elif name == "logloss":
                 v = rec[:, 0].astype(np.float64) / R.LOSS_SCALE / rows
             elif name == "error":
                 v = rec[:, 1].astype(np.float64) / rows
@@ -336,7 +345,8 @@ class _Eval:
         best_score = hist[self.metrics[-1]][self.best] if k else float("nan")
         return EvalRecord(history=hist, best_iteration=int(self.best), best_score=float(best_score),
                           metrics=tuple(self.metrics), records=rec, twice_pairs=tw if self.want_auc else None,
-                          stopped=self.stop_at is not None, ap_q=aq if self.want_aucpr else None)
+                          stopped=self.stop_at is not None, ap_q=aq if self.want_aucpr else None,
+                          weight_q=self.weight_q)
 
 
 def _eval_request(eval_set, eval_metric, early_stopping_rounds, hole_len, checkpoint, dist, T):
@@ -393,11 +403,45 @@ def _resume(checkpoint, sig, T):
     return {k: v.numpy()[:t0] for k, v in tensors.items()}, t0
 
 
+def _weights_arg(w, rows: int, dev: torch.device, name: str) -> torch.Tensor:
+    if not isinstance(w, torch.Tensor) or w.dtype != torch.float32 or w.dim() != 1 or w.shape[0] != rows:
+        raise ValueError(f"{name} must be a float32 tensor of shape [{rows}] (one weight per row)")
+    if w.device != dev:
+        raise ValueError(f"{name} must be on the fit's device ({dev}), got {w.device}")
+    return w.contiguous()
+
+
+def _weight_stats(w: torch.Tensor, y: torch.Tensor | None, ha: int, hl: int, spw: float, comm, name: str):
+    """(wmax, smallest positive w_eff) of a fit's weights -- the table rows without the hole, all
+    ranks -- after refusing NaN, infinite, negative and all-zero weights: one device reduction
+    (gbdt.hip gbdt_weight_stats_kernel) and one host read."""
+    n = int(w.shape[0])
+    if not w.is_cuda:
+        keep = np.r_[0:ha, ha + hl:n]
+        wmax, effmin, bad = R.weight_stats(w.numpy()[keep], None if y is None else y.numpy()[keep], spw)
+    else:
+        out = torch.tensor([0, 0x7FF0000000000000, 0], dtype=torch.int64, device=w.device)
+        native().gbdt_weight_stats(ptr(w), 0 if y is None else ptr(y), n, ha, hl, spw, ptr(out), stream_of(w))
+        o = out.cpu().numpy()
+        wmax = float(o[:1].astype(np.uint32).view(np.float32)[0])
+        effmin, bad = float(o[1:2].view(np.float64)[0]), int(o[2])
+    if comm is not None and comm.world_size > 1:  # every rank raises, or none does
+        wmax = comm.all_reduce_scalar(wmax, "max")
+        effmin = comm.all_reduce_scalar(effmin, "min")
+        bad = int(comm.all_reduce_scalar(float(bad)))
+    if bad:
+        raise ValueError(f"{name} must be finite and >= 0 ({bad} entries are NaN, infinite or negative)")
+    if not wmax > 0.0:
+        raise ValueError(f"{name}: no row has a positive weight")
+    return wmax, effmin
+
+
 def fit(X: torch.Tensor, y: torch.Tensor, params: GBDTParams | None = None, comm=None,
         cuts=None, sample_weight_pos: float | None = None, return_margin: bool = False,
         checkpoint=None, checkpoint_every: int = 10, use_graph: bool | None = None,
         eval_set=None, eval_metric=("logloss",), early_stopping_rounds: int | None = None,
-        row_offset: int | None = None):
+        row_offset: int | None = None, sample_weight: torch.Tensor | None = None,
+        eval_sample_weight: torch.Tensor | None = None):
     """Boost `n_estimators` depth-D trees on standardized float32 rows X [n, d] with labels y.
 
     ``checkpoint``: a utils.checkpoint.CheckpointManager.  Every ``checkpoint_every`` rounds the
@@ -405,8 +449,9 @@ def fit(X: torch.Tensor, y: torch.Tensor, params: GBDTParams | None = None, comm
     round.  Training margins are recomputed from the saved trees over the same bins, so a resumed
     fit is bit-identical to an uninterrupted one.
 
-    ``eval_set`` / ``eval_metric`` / ``early_stopping_rounds`` / ``row_offset``: see fit_binned; with
-    an eval set the return value gains an EvalRecord as its last element."""
+    ``eval_set`` / ``eval_metric`` / ``early_stopping_rounds`` / ``row_offset`` / ``sample_weight`` /
+    ``eval_sample_weight``: see fit_binned; with an eval set the return value gains an EvalRecord as
+    its last element.  The quantile cuts computed here are unweighted."""
     p = (params or GBDTParams()).validate()
     n, d = X.shape
     if d > MAX_FEAT:
@@ -417,14 +462,15 @@ def fit(X: torch.Tensor, y: torch.Tensor, params: GBDTParams | None = None, comm
     return fit_binned(bins, y, cuts, p, comm=comm, sample_weight_pos=sample_weight_pos, return_margin=return_margin,
                       checkpoint=checkpoint, checkpoint_every=checkpoint_every, use_graph=use_graph,
                       eval_set=eval_set, eval_metric=eval_metric, early_stopping_rounds=early_stopping_rounds,
-                      row_offset=row_offset)
+                      row_offset=row_offset, sample_weight=sample_weight, eval_sample_weight=eval_sample_weight)
 
 
 def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | None = None, comm=None,
                sample_weight_pos: float | None = None, return_margin: bool = False, checkpoint=None,
                checkpoint_every: int = 10, use_graph: bool | None = None, hole: tuple | None = None,
                eval_set=None, eval_metric=("logloss",), early_stopping_rounds: int | None = None,
-               row_offset: int | None = None):
+               row_offset: int | None = None, sample_weight: torch.Tensor | None = None,
+               eval_sample_weight: torch.Tensor | None = None):
     """Boosting on already-binned rows (u8 [n, 32], bin_rows) with their cuts (cuts, nbins).
 
     ``hole``: (at, len) -- the fit's rows are the table without the block [at, at + len) (a
@@ -466,7 +512,33 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
     fall back to the eager, unfused round: the round number t, which selects the row sample and the
     row of the mask table, is a launch argument that changes every round: a captured graph would
     replay the value of the round it was recorded in, and the fused level-0 pass (gbdt_hist_l0_fused)
-    computes the gradients itself and has no sampled variant."""
+    computes the gradients itself and has no sampled variant.
+
+    Per-row weights (``sample_weight``): a float32 [n] tensor on the bins' device, one weight per
+    TABLE row, finite and >= 0 with at least one positive among the fit's rows (entries inside a
+    ``hole`` are ignored for training).  A row's effective weight is w_eff = w * (y ? scale_pos_weight
+    : 1), and its gradient pair g = (p - y) w_eff, h = max(p (1 - p), 1e-16) w_eff is formed in fp64
+    before the quantisation; histograms, split scan, partition and leaves work on the integers as
+    before, bitwise deterministic.  The fixed-point scale is gscale = 2^floor(log2(2^14 / W)), W =
+    max(scale_pos_weight, 1) * wmax with wmax the largest weight over the fit's rows (all ranks; one
+    device reduction and one host read per fit, no round waits for the host), hscale = 4 gscale: an
+    all-ones fit is the unweighted fit bit for bit.  Resolution: the packed (g, h) word has 14 bits,
+    so a row with w_eff * gscale < 16 has fewer than 16 quanta of gradient even at |p - y| = 1 and
+    its contribution is coarsely rounded; the fit issues one UserWarning naming the ratio when the
+    smallest positive w_eff is that far (more than 2^10) below the largest.  A row of weight 0 stays
+    in the table, takes every margin update and every partition and adds nothing to any histogram;
+    with ``subsample`` an out-of-sample row's word is 0 whatever its weight.  The quantile cuts stay
+    unweighted (xgboost's sketch is Hessian-weighted).  With weights, as under sampling, the
+    hipGraph path and FDX_GBDT_FUSE_MARGIN=1 fall back to the eager, unfused round
+    (gbdt_hist_l0_fused has no weighted variant).  ``checkpoint=`` with ``sample_weight`` raises
+    NotImplementedError: the signature would have to cover the weights.
+
+    Evaluation weights (``eval_sample_weight``, xgboost's sample_weight_eval_set): float32 [m] for an
+    ``(Xv, yv)`` set, [hole_len] for ``eval_set="hole"``, finite and >= 0 with a positive entry.
+    "logloss" and "error" become weighted means and stay exact integers
+    (reference_gbdt.eval_record_weighted; EvalRecord.weight_q is the denominator); the stop rule
+    compares the integer numerators, the denominator being constant.  "auc" and "aucpr" with
+    evaluation weights raise NotImplementedError (their kernels count pairs and tie groups)."""
     p = (params or GBDTParams()).validate()
     cuts_np, nbins = cuts
     d = int(len(nbins))
@@ -480,7 +552,19 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
         raise ValueError(f"hole {hole} outside the {n} table rows")
     n_fit = n - hl
     spw = float(p.scale_pos_weight if sample_weight_pos is None else sample_weight_pos)
-    gscale, hscale = R.grad_scales(spw)
+    wt, wmax = None, 1.0
+    if sample_weight is not None:
+        if checkpoint is not None:
+            raise NotImplementedError("checkpoint= cannot be combined with sample_weight: the checkpoint's "
+                                      "signature does not cover the weights")
+        wt = _weights_arg(sample_weight, n, bins.device, "sample_weight")
+        wmax, eff_min = _weight_stats(wt, y, ha, hl, spw, comm, "sample_weight")
+    gscale, hscale = R.grad_scales(spw, wmax)
+    if wt is not None and eff_min * gscale < R.WEIGHT_MIN_QUANTA:
+        warnings.warn(f"sample_weight: the smallest positive effective weight {eff_min:.3g} times the gradient "
+                      f"scale {gscale:g} is {eff_min * gscale:.3g} < {R.WEIGHT_MIN_QUANTA:g}: such rows have fewer "
+                      f"than {R.WEIGHT_MIN_QUANTA:g} quanta of gradient (14-bit fixed point, largest effective "
+                      f"weight {max(spw, 1.0) * wmax:.3g})", UserWarning, stacklevel=2)
     D = p.max_depth
     ni, nl = (1 << D) - 1, 1 << D
     T = p.n_estimators
@@ -516,6 +600,19 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
                     raise ValueError(f"eval_set: the fit has {d} features, Xv has {tuple(Xv.shape)}")
                 bins_v = bin_rows(Xv if Xv.is_cuda else Xv.float(), cuts_np, nbins)
             yv = yv.contiguous()
+    w_ev = None
+    if eval_sample_weight is not None:
+        if ev is None:
+            raise ValueError("eval_sample_weight needs an eval_set")
+        if ev.want_auc or ev.want_aucpr:
+            raise NotImplementedError("eval_metric 'auc' / 'aucpr' do not take evaluation weights "
+                                      "(their kernels count pairs and tie groups); use 'logloss' or 'error'")
+        w_ev = _weights_arg(eval_sample_weight, hl if ev_kind == "hole" else int(yv.shape[0]), bins.device,
+                            "eval_sample_weight")
+        ev_wscale = R.eval_weight_scale(_weight_stats(w_ev, None, 0, 0, 1.0, comm, "eval_sample_weight")[0])
+        # wsum_q, a constant of the eval set: an exact int64 sum, once per fit
+        wq = torch.round(w_ev.double() * (ev_wscale * R.EVAL_WEIGHT_SCALE)).to(torch.int64).sum().reshape(1)
+        ev.weight_q = int((comm.all_reduce(wq) if dist else wq).item())
     sig = None
     if checkpoint is not None:
         from ..utils.checkpoint import config_signature
@@ -554,6 +651,7 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
         y_all = y.numpy()
         keep = np.r_[0:ha, ha + hl:n]
         b, yy = b_all[keep], y_all[keep]
+        ww = None if wt is None else wt.numpy()[keep]
         margin = np.full(n_fit, np.float32(base_margin), np.float32)
         if t0:
             feat[:t0], binv[:t0], thr[:t0], gain[:t0], leaf[:t0] = (prev[k] for k in ("feat", "bin", "thr", "gain", "leaf"))
@@ -562,7 +660,7 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
             b_ev, y_ev = (b_all[ha:ha + hl], y_all[ha:ha + hl]) if ev_kind == "hole" else (bins_v.numpy(), yv.numpy())
             m_ev = np.full(b_ev.shape[0], np.float32(base_margin), np.float32)
         for t in range(t0, T):
-            q = R.gradients(margin, yy, spw, gscale, hscale)
+            q = R.gradients(margin, yy, spw, gscale, hscale, ww)
             if sub_on:  # global ids of the fit's rows: a row keeps its table index around the hole
                 q[~R.row_sample_mask(seed, t, keep + row_offset, p.subsample)] = 0
             tr, node = R.build_tree(b, q, cuts_np, nbins, D, p.reg_lambda, p.min_child_weight, p.gamma,
@@ -574,7 +672,8 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
             if ev is not None:
                 m_ev = (m_ev + R.predict_margin_bins(b_ev, feat[t:t + 1], binv[t:t + 1], leaf[t:t + 1], D, 0.0)
                         ).astype(np.float32)
-                rec = R.eval_record(m_ev, y_ev)
+                rec = R.eval_record(m_ev, y_ev) if w_ev is None else \
+                    R.eval_record_weighted(m_ev, y_ev, w_ev.numpy(), ev_wscale)
                 if comm is not None and comm.world_size > 1:
                     rec = comm.all_reduce(torch.from_numpy(rec)).numpy()
                 if ev.push(rec, R.twice_pairs(m_ev, y_ev) if ev.want_auc else 0,
@@ -633,7 +732,12 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
         ``t``: the round, read only under sampling (round t's row sample goes into the gradients
         that round t - 1's margin walk writes; round t's feature masks into its split scans)."""
         st = stream_of(bins)  # the capture stream while a hipGraph is being recorded
-        if grad_first and sub_on:
+        if grad_first and wt is not None and sub_on:
+            m.gbdt_grad_sampled_weighted(ptr(margin), ptr(y), ptr(wt), n, spw, gscale, hscale, ptr(ws.gh), seed, t,
+                                         row_offset, thresh, st)
+        elif grad_first and wt is not None:
+            m.gbdt_grad_weighted(ptr(margin), ptr(y), ptr(wt), n, spw, gscale, hscale, ptr(ws.gh), st)
+        elif grad_first and sub_on:
             m.gbdt_grad_sampled(ptr(margin), ptr(y), n, spw, gscale, hscale, ptr(ws.gh), seed, t, row_offset, thresh, st)
         elif grad_first:
             m.gbdt_grad(ptr(margin), ptr(y), n, spw, gscale, hscale, ptr(ws.gh), st)
@@ -671,7 +775,14 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
             if dist:
                 comm.all_reduce_(ws.gcnt[c0:c0 + 2 * nn])
         m.gbdt_leaf(ptr(ws.ng), ptr(ws.nh), D, ginv, hinv, lam, mcw, float(p.learning_rate), ptr(o_leaf), st)
-        if n and not defer_margin and grad_next and sub_on:
+        if n and not defer_margin and grad_next and wt is not None and sub_on:
+            m.gbdt_margin_sampled_weighted(ptr(binsT), ldt, n, ptr(o_feat), ptr(o_bin), ptr(o_leaf), D, ptr(margin),
+                                           ptr(y), ptr(wt), spw, gscale, hscale, ptr(ws.gh), seed, t + 1, row_offset,
+                                           thresh, st)
+        elif n and not defer_margin and grad_next and wt is not None:
+            m.gbdt_margin_weighted(ptr(binsT), ldt, n, ptr(o_feat), ptr(o_bin), ptr(o_leaf), D, ptr(margin), ptr(y),
+                                   ptr(wt), spw, gscale, hscale, ptr(ws.gh), st)
+        elif n and not defer_margin and grad_next and sub_on:
             m.gbdt_margin_sampled(ptr(binsT), ldt, n, ptr(o_feat), ptr(o_bin), ptr(o_leaf), D, ptr(margin), ptr(y), spw,
                                   gscale, hscale, ptr(ws.gh), seed, t + 1, row_offset, thresh, st)
         elif n and not defer_margin:
@@ -695,9 +806,10 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
     # off too (the hole's margins must be current when the round's record is taken).
     # Sampling keeps them too, unfused: a recorded round and the fused level-0 pass bake the round's
     # constants in, and the round number (row sample, mask row) is one of them.
-    graphable = use_graph and not dist and n > 0 and T - t0 >= 3 and ev is None and not p.sampled
+    # Per-row weights keep them as well: the fused level-0 pass has no weighted variant.
+    graphable = use_graph and not dist and n > 0 and T - t0 >= 3 and ev is None and not p.sampled and wt is None
     fuse_margin = (os.environ.get("FDX_GBDT_FUSE_MARGIN", "0") == "1" and not graphable and ev is None
-                   and not p.sampled)
+                   and not p.sampled and wt is None)
     graph = None
     if ev is not None:
         from . import metrics as metric_ops
@@ -727,9 +839,16 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
 
         def eval_round(t):
             st = stream_of(bins)
-            if ev_kind == "set":
+            if ev_kind == "set" and w_ev is not None:
+                m.gbdt_eval_walk_weighted(ptr(binsT_v), ldt_v, nv, ptr(feat[t]), ptr(binv[t]), ptr(leaf[t]), D,
+                                          ptr(m_ev), ptr(y_ev), ptr(w_ev), ev_wscale, ptr(ev_hist[t]), st)
+            elif ev_kind == "set":
                 m.gbdt_eval_walk(ptr(binsT_v), ldt_v, nv, ptr(feat[t]), ptr(binv[t]), ptr(leaf[t]), D, ptr(m_ev),
                                  ptr(y_ev), ptr(ev_hist[t]), st)
+            elif w_ev is not None:
+                # the kernel indexes the weights by TABLE row like margin and label: hole row r reads
+                # w_ev[r - ha], so the pointer is moved back by ha entries (never read below the hole)
+                m.gbdt_eval_weighted(ptr(margin), ptr(y), ptr(w_ev) - 4 * ha, ev_wscale, ha, ha + hl, ptr(ev_hist[t]), st)
             else:
                 m.gbdt_eval(ptr(margin), ptr(y), ha, ha + hl, ptr(ev_hist[t]), st)
             if dist:

@@ -74,23 +74,52 @@ def bin_rows(X: np.ndarray, cuts: np.ndarray, nbins: np.ndarray) -> np.ndarray:
 GRAD_BITS = 14  # |g_q|, h_q <= 2^14: the device packs (h, g) of a row into one 64-bit LDS atomic
 
 
-def grad_scales(scale_pos_weight: float):
+def grad_scales(scale_pos_weight: float, wmax: float = 1.0):
     """Power-of-two fixed-point scales with |g * gscale| <= 2^14 and h * hscale <= 2^14
-    (h = p (1 - p) w <= w / 4): 2^16 rows of packed (h << 32) + g sum exactly in 64 bits."""
-    wmax = max(float(scale_pos_weight), 1.0)
-    gscale = float(2.0 ** np.floor(np.log2((2.0 ** GRAD_BITS) / wmax)))
+    (h = p (1 - p) w <= w / 4): 2^16 rows of packed (h << 32) + g sum exactly in 64 bits.
+    ``wmax``: the largest per-row sample weight of the fit (all ranks); the largest effective
+    weight is W = max(scale_pos_weight, 1) * wmax.  With wmax = 1 (no weights, or all ones) the
+    scales are what they always were."""
+    W = max(float(scale_pos_weight), 1.0) * float(wmax)
+    gscale = float(2.0 ** np.floor(np.log2((2.0 ** GRAD_BITS) / W)))
     return gscale, 4.0 * gscale
 
 
-def gradients(margin: np.ndarray, y: np.ndarray, spw: float, gscale: float, hscale: float) -> np.ndarray:
-    """int32 [n, 2] quantised (g, h) of the logistic loss (fp64 arithmetic on fp32 margins)."""
+def effective_weights(y: np.ndarray, spw: float, weight=None) -> np.ndarray:
+    """fp64 [n]: w_eff = (double)w_i * (y_i ? (double)(float)spw : 1.0), w_i float32 (None: 1)."""
+    pos = np.asarray(y) != 0
+    w = np.where(pos, float(np.float32(spw)), 1.0)
+    if weight is not None:
+        w = np.asarray(weight, dtype=np.float32).astype(np.float64) * w
+    return w
+
+
+def gradients(margin: np.ndarray, y: np.ndarray, spw: float, gscale: float, hscale: float, weight=None) -> np.ndarray:
+    """int32 [n, 2] quantised (g, h) of the logistic loss (fp64 arithmetic on fp32 margins).
+    ``weight``: float32 [n] per-row sample weights, one more exact factor in front of the
+    quantisation: g = (p - y) w_eff, h = max(p (1 - p), 1e-16) w_eff (effective_weights)."""
     m = np.asarray(margin, dtype=np.float32).astype(np.float64)
     p = 1.0 / (1.0 + np.exp(-m))
     pos = np.asarray(y) != 0
-    w = np.where(pos, float(np.float32(spw)), 1.0)
+    w = effective_weights(y, spw, weight)
     g = (p - pos.astype(np.float64)) * w
     h = np.maximum(p * (1.0 - p), 1e-16) * w
     return np.stack([np.rint(g * gscale), np.rint(h * hscale)], 1).astype(np.int32)
+
+
+WEIGHT_MIN_QUANTA = 16.0  # a row with w_eff * gscale below this has < 16 quanta of gradient at full scale
+
+
+def weight_stats(weight: np.ndarray, y=None, spw: float = 1.0):
+    """(wmax, smallest positive w_eff or +inf, count of NaN / infinite / negative entries) of
+    float32 weights -- what a fit validates and scales by (gbdt.hip gbdt_weight_stats_kernel)."""
+    w = np.asarray(weight, dtype=np.float32)
+    bad = ~(w >= 0) | np.isinf(w)
+    ok = w[~bad]
+    wmax = float(ok.max()) if ok.size else 0.0
+    eff = effective_weights(y, spw, w)[~bad] if y is not None else ok.astype(np.float64)
+    eff = eff[ok > 0]
+    return wmax, (float(eff.min()) if eff.size else float("inf")), int(bad.sum())
 
 
 def _hist(bins: np.ndarray, q: np.ndarray, node: np.ndarray, nn: int, d: int) -> np.ndarray:
@@ -334,6 +363,42 @@ def eval_record(margin: np.ndarray, y: np.ndarray) -> np.ndarray:
         sp = np.maximum(z, 0.0) + np.log1p(np.exp(-np.abs(z)))
     q = np.rint(np.fmin(sp, LOSS_CAP) * LOSS_SCALE).astype(np.int64)
     return np.array([q.sum(), np.count_nonzero((m > 0.0) != pos), np.count_nonzero(pos), m.shape[0]], dtype=np.int64)
+
+
+EVAL_WEIGHT_BITS = 16   # u = w * wscale <= 2^16
+EVAL_WEIGHT_SCALE = float(2 ** 14)  # 2^16 * 2^14 = LOSS_SCALE: unit weights give the unweighted loss terms
+
+
+def eval_weight_scale(wmax: float) -> float:
+    """wscale = 2^floor(log2(2^16 / wmax)) for the largest eval weight (all ranks), wmax > 0."""
+    return float(2.0 ** np.floor(np.log2((2.0 ** EVAL_WEIGHT_BITS) / float(wmax))))
+
+
+def eval_weight_q(w: np.ndarray, wscale: float) -> np.ndarray:
+    """int64 [m]: rint(u * 2^14), u = w * wscale (exact: a power of two times an fp32) -- a row's
+    term of the weight sum wsum_q and of the weighted error sum."""
+    u = np.asarray(w, dtype=np.float32).astype(np.float64).ravel() * float(wscale)
+    return np.rint(u * EVAL_WEIGHT_SCALE).astype(np.int64)
+
+
+def eval_record_weighted(margin: np.ndarray, y: np.ndarray, w: np.ndarray, wscale: float) -> np.ndarray:
+    """int64 [4] = (loss_q, err_q, n_pos, n_rows) with per-row weights (xgboost's
+    sample_weight_eval_set) -- the oracle of gbdt.hip's weighted gbdt_eval_kernel.  With
+    u = w * wscale <= 2^16: loss_q = sum rint(min(softplus, cap) * u * 2^14) and err_q = sum over
+    the error rows of rint(u * 2^14); n_pos and n_rows are counts as in eval_record.  The metrics
+    divide by wsum_q = eval_weight_q(w, wscale).sum(): logloss = loss_q / wsum_q, error = err_q /
+    wsum_q.  All weights equal to the largest one (u = 2^16) give eval_record's loss_q."""
+    m = np.asarray(margin, dtype=np.float32).astype(np.float64).ravel()
+    pos = np.asarray(y).ravel() != 0
+    if m.shape[0] > EVAL_MAX_ROWS:
+        raise ValueError("at most 2^27 eval rows")
+    u = np.asarray(w, dtype=np.float32).astype(np.float64).ravel() * float(wscale)
+    z = np.where(pos, -m, m)
+    with np.errstate(over="ignore"):
+        sp = np.maximum(z, 0.0) + np.log1p(np.exp(-np.abs(z)))
+    q = np.rint(np.fmin(sp, LOSS_CAP) * u * EVAL_WEIGHT_SCALE).astype(np.int64)
+    eq = np.rint(u * EVAL_WEIGHT_SCALE).astype(np.int64)
+    return np.array([q.sum(), eq[(m > 0.0) != pos].sum(), np.count_nonzero(pos), m.shape[0]], dtype=np.int64)
 
 
 def twice_pairs(margin: np.ndarray, y: np.ndarray) -> int:

@@ -3,7 +3,11 @@
 credit_card-shaped synthetic rows after SMOTE, plus test AUC and inference rate.
 
     python tools/gbdt_bench.py [--rows 10000000] [--trees 100] [--json out.json]
-                               [--subsample 0.8] [--colsample-bytree 0.5] [--seed 0]
+                               [--subsample 0.8] [--colsample-bytree 0.5] [--seed 0] [--weights]
+
+--weights: every table row of the boosting call gets a sample weight (a time decay from 0.25 for the
+first row to 1.0 for the last, SMOTE's rows included), to measure what the weighted kernels cost on
+the same rows.  The pipeline itself takes no weights: the tool hands them to its ops/gbdt.fit call.
 """
 from __future__ import annotations
 
@@ -27,6 +31,7 @@ def main():
     ap.add_argument("--subsample", type=float, default=1.0)
     ap.add_argument("--colsample-bytree", type=float, default=1.0)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--weights", action="store_true")
     a = ap.parse_args()
     from fraud_detection_amd.data.synthetic import separable
     from fraud_detection_amd.models.gbdt import GBDTPipeline
@@ -34,6 +39,14 @@ def main():
     from fraud_detection_amd.ops import gbdt as gb
 
     dev = torch.device("cuda", 0)
+    if a.weights:
+        fit = gb.fit
+
+        def weighted_fit(rows, labels, params, **kw):
+            w = torch.linspace(0.25, 1.0, rows.shape[0], dtype=torch.float32, device=rows.device)
+            return fit(rows, labels, params, sample_weight=w, **kw)
+
+        gb.fit = weighted_fit  # models/gbdt.py calls gb.fit: the pipeline's rows, plus a weight each
     n_test = a.rows // 5
     X, y = separable(a.rows - n_test, seed=1000, device=dev)
     Xt, yt = separable(n_test, seed=5000, device=dev)
@@ -62,6 +75,8 @@ def main():
            "scale_pos_weight": round(res.scale_pos_weight, 3)}
     if pipe.params.sampled:
         out.update(sampling)
+    if a.weights:
+        out["weights"] = "linspace(0.25, 1.0)"
     print(json.dumps(out))
     if a.json:
         with open(a.json, "w") as f:
