@@ -146,7 +146,10 @@ def tree_explain(X_test, names, n) -> dict:
         ens = TreeEnsemble.from_dict(json.load(f))
     d = X_test.shape[1]
     bg = X_test[np.random.default_rng(1).choice(len(X_test), min(100, len(X_test)), replace=False)]
-    te = TreeExplainer(ens, np.zeros(d), np.ones(d), bg)
+    try:
+        te = TreeExplainer(ens, np.zeros(d), np.ones(d), bg)
+    except ValueError as e:  # e.g. a model trained on other columns than the data file holds
+        raise SystemExit(f"--tree: {path} does not fit the test rows: {e}")
     rows = X_test[:n]
     phi, fx, f0 = te.explain(rows)
     summary_plot(phi, rows, names, "plots/treeshap_summary.png")

@@ -318,9 +318,23 @@ def kernelshap_tree_reference(Xs: np.ndarray, Bs: np.ndarray, ens, Z: np.ndarray
     return _project(f, f0, fx, A, zM), fx, f0
 
 
+def _check_tree_features(ens, d: int) -> None:
+    """The tree kernels index a 32-bit coalition mask and a [d]-row table by split feature: a model
+    whose features do not fit the data's width must not reach them."""
+    if d > 30:
+        raise ValueError(f"tree explainers support at most 30 features, the background has {d}")
+    fmin, fmax = int(ens.feat.min()), int(ens.feat.max())
+    if fmin < -1:
+        raise ValueError(f"tree ensemble has split feature {fmin}: only -1 (pass-through) may be negative")
+    if fmax >= d:
+        raise ValueError(f"tree ensemble splits on feature {fmax} (a model of at least {fmax + 1} features) "
+                         f"but the background has {d} columns")
+
+
 class TreeKernelExplainer:
     """KernelSHAP of a tree ensemble (ops/gbdt.TreeEnsemble trained on standardized rows) over RAW
-    inputs: the model is standardize -> ensemble, as served.  Background: <= 128 raw rows."""
+    inputs: the model is standardize -> ensemble, as served.  Background: <= 128 raw rows of the
+    width the model was trained on (at most 30 columns, every split feature among them)."""
 
     def __init__(self, ens, mean, scale, background: np.ndarray, nsamples: int | None = None,
                  link: str = "identity", seed: int = 0, device="auto"):
@@ -329,6 +343,7 @@ class TreeKernelExplainer:
             raise ValueError("at most 128 background rows (summarize larger sets)")
         if ens.depth > 5:
             raise ValueError("tree KernelSHAP supports depth <= 5 (the reference trains max_depth=5)")
+        _check_tree_features(ens, B.shape[1])
         self.ens = ens
         self.d = B.shape[1]
         self.mean = np.asarray(mean, np.float64)
@@ -429,7 +444,8 @@ class TreeExplainer:
     """Interventional TreeSHAP of a tree ensemble (ops/gbdt.TreeEnsemble on standardized rows)
     over RAW inputs, in margin (log-odds) space -- shap.TreeExplainer(model, data=background,
     feature_perturbation="interventional") semantics, exact (no coalition sampling): the fast
-    explainer of the GBDT family (csrc/kernels/treeshap.hip).  Background: <= 1024 raw rows."""
+    explainer of the GBDT family (csrc/kernels/treeshap.hip).  Background: <= 1024 raw rows of
+    the width the model was trained on (at most 30 columns, every split feature among them)."""
 
     link = "logit_model"
 
@@ -439,6 +455,7 @@ class TreeExplainer:
             raise ValueError("1..1024 background rows")
         if ens.depth > 5:
             raise ValueError("TreeSHAP kernel supports depth <= 5 (the reference trains max_depth=5)")
+        _check_tree_features(ens, B.shape[1])
         self.ens = ens
         self.d = B.shape[1]
         self.mean = np.asarray(mean, np.float64)

@@ -38,9 +38,13 @@ def treeshap(X: torch.Tensor, expl, sync: bool = True, out=None):
     from .scaler import scale_cast
 
     E = X.shape[0]
-    Xs = scale_cast(X, t["stats"], out_dtype="f32")  # [E, 32]
     phi, fx, f0 = _outputs(E, expl.d, dev, out)
     ens = expl.ens
+    if E == 0:  # nothing to launch: empty results of the documented shapes
+        if not sync:
+            return phi, fx, f0
+        return np.zeros((0, expl.d)), np.zeros(0), float(expl.f0)
+    Xs = scale_cast(X, t["stats"], out_dtype="f32")  # [E, 32]
     m.treeshap(ptr(Xs), Xs.stride(0), E, expl.d, ptr(t["feat"]), ptr(t["thr"]), ptr(t["leaf"]), ens.n_trees,
                ens.depth, float(ens.base_margin), ptr(t["bw"]), expl.bw.shape[1], expl.B.shape[0], float(expl.f0),
                ptr(phi), ptr(fx), ptr(f0), stream_of(X))

@@ -3,7 +3,9 @@
 CPU: the three explainers agree with each other (linear fast path vs the generic masked-row
 path; tree-ensemble walk vs the generic path over the same ensemble) and satisfy efficiency.
 GPU: the linear MFMA kernel and the tree kernel match their fp64 oracles and are deterministic for
-a given coalition-part count (the last-arriver reduction sums partials in part order).
+a given coalition-part count (the last-arriver reduction sums partials in part order); on a fully
+enumerated design (d = 8) the tree kernel equals brute-force Shapley values and device TreeSHAP
+within the derived bounds of tests/_tree_cases.py, at every depth and on both leaf memory paths.
 """
 import numpy as np
 import pytest
@@ -150,6 +152,66 @@ def test_tree_kernel_matches_oracle(dev, depth, trees, nbg):
     assert abs(f0 - ref[2]) < 1e-6
     np.testing.assert_allclose(phi, ref[0], atol=2e-5)
     np.testing.assert_allclose(phi.sum(1), fx - f0, atol=1e-5)
+
+
+def _enumerated_tree_case(dev, depth, T, E=2, d=8, n_bg=6):
+    """A random ensemble over d = 8 features under a design that enumerates all 2^8 - 2 proper
+    coalitions, identity scaler (the oracle sees the device's fp32 rows bit for bit)."""
+    import _tree_cases as TC
+
+    ens = TC.random_ensemble(d, depth, T, 300 + 10 * depth + T)
+    Xs, Bs = TC.random_rows(d, E, n_bg, 301 + depth)
+    tk = EX.TreeKernelExplainer(ens, np.zeros(d), np.ones(d), Bs, nsamples=4096, link="logit_model", device=str(dev))
+    assert tk.nsamples == 2 ** d - 2  # every coalition: the WLS solution is the Shapley vector
+    return ens, Xs, Bs, tk
+
+
+def _assert_tree_kernel_is_shapley(dev, ens, Xs, Bs, tk, parts, what):
+    """Device kernelshap_tree against brute-force Shapley within _tree_cases.kernelshap_tree_bound,
+    and against device TreeSHAP within the sum of both kernels' bounds."""
+    import _tree_cases as TC
+    from fraud_detection_amd.ops.kernelshap import kernelshap_tree
+
+    d, n_bg = Xs.shape[1], len(Bs)
+    phi, fx, f0 = kernelshap_tree(torch.from_numpy(Xs).to(dev), tk, parts=parts)
+    kb = TC.kernelshap_tree_bound(Xs, Bs, ens, tk.Z, tk.A, tk.zM, parts)
+    assert np.all(kb["phi"] <= TC.kernelshap_any_order_bound(tk.A, ens, n_bg)[None, :])  # the tighter of the two
+    brute = TC.brute_force_shapley(Xs, Bs, ens)
+    np.testing.assert_allclose(kb["shapley"], brute, rtol=0, atol=1e-10)  # the enumerated design is exact
+    TC.assert_within(phi, brute, kb["phi"], f"{what} phi vs brute force")
+    st = TC.walk_stats(Xs, Bs, ens)
+    ts = EX.TreeExplainer(ens, np.zeros(d), np.ones(d), Bs, device=str(dev)).explain(Xs)
+    TC.assert_within(phi, ts[0], kb["phi"] + TC.phi_bound(st["S"], ens.n_trees, n_bg, ens.depth),
+                     f"{what} phi vs treeshap")
+    TC.assert_within(fx - f0, st["fx"] - st["f0"], kb["delta"], f"{what} delta")
+    # the kernel sets phi[d-1] = delta - (phi[0] + ... + phi[d-2]) in fp32: d roundings of partial
+    # sums no larger than |delta| + sum |phi|
+    TC.assert_within(phi.sum(1), fx - f0, d * TC.U * (np.abs(fx - f0) + np.abs(phi).sum(1)), f"{what} efficiency")
+    return phi
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("depth", [1, 2, 3, 4, 5])
+def test_tree_kernel_equals_shapley_on_enumerated_design(dev, depth):
+    """Every depth instantiation of the tree KernelSHAP kernel, log-odds link, one and four
+    coalition parts: two device kernels (this one and TreeSHAP) and brute force, one answer."""
+    ens, Xs, Bs, tk = _enumerated_tree_case(dev, depth, 12)
+    p1 = _assert_tree_kernel_is_shapley(dev, ens, Xs, Bs, tk, 1, f"tree kernel depth {depth} parts 1")
+    p4 = _assert_tree_kernel_is_shapley(dev, ens, Xs, Bs, tk, 4, f"tree kernel depth {depth} parts 4")
+    assert np.abs(p1).max() > 1e-3 and np.abs(p4).max() > 1e-3  # a non-trivial explanation
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("over", [0, 1])
+def test_tree_kernel_leaves_in_lds_and_in_global_memory(dev, over):
+    """T * 2^depth crosses the kernel's LDS leaf capacity by one tree: 256 trees of depth 5 are
+    staged in LDS, 257 are read from global memory."""
+    import _tree_cases as TC
+
+    T = TC.KS_LDS_LEAVES // 32 + over
+    assert (T << 5 <= TC.KS_LDS_LEAVES) == (over == 0) and T == 256 + over
+    ens, Xs, Bs, tk = _enumerated_tree_case(dev, 5, T)
+    _assert_tree_kernel_is_shapley(dev, ens, Xs, Bs, tk, 4, f"tree kernel T {T}")
 
 
 # ---------------------------------------------------------------------------------------------

@@ -75,3 +75,23 @@ def test_explain_model_tree_shap_of_a_gbdt(workdir):
     assert "treeshap_rows" in out
     phi = np.load(workdir / "plots" / "treeshap_values.npy")
     assert phi.shape == (50, 30) and (workdir / "plots" / "treeshap_summary.png").exists()
+
+
+def test_explain_model_tree_refuses_a_model_of_another_width(workdir, monkeypatch):
+    """A GBDT file that splits on a column the data file does not have is refused by name, before
+    any kernel sees it (in process: the refusal is the explainer's, raised on construction)."""
+    import json
+
+    from test_treeshap import random_ensemble
+
+    import explain_model
+
+    ens = random_ensemble(31, 3, 4, 5, p_pass=0.0)
+    ens.feat[0, 0] = 30
+    with open(workdir / "models" / "xgb_model.json", "w") as f:
+        json.dump(ens.to_dict(), f)
+    monkeypatch.chdir(workdir)
+    X = np.zeros((20, 30), np.float32)
+    with pytest.raises(SystemExit) as ei:
+        explain_model.tree_explain(X, [f"f{i}" for i in range(30)], 5)
+    assert "31 features" in str(ei.value) and "30 columns" in str(ei.value)
