@@ -510,25 +510,82 @@ def _newton_fuse() -> bool:
 
 
 def logreg_pass(rows: torch.Tensor, w: torch.Tensor, class_w=(1.0, 1.0), hessian: bool = True,
-                fp8_scale: float = DEFAULT_FP8_SCALE, virtual: VirtualSmote | None = None):
+                fp8_scale: float = DEFAULT_FP8_SCALE, virtual: VirtualSmote | None = None, *,
+                hess_stride: int = 1, sub: int = 1, hole: tuple | None = None, nblocks: int | None = None,
+                full: bool = False):
     """One reduced pass: (grad[32], loss, wsum, H[32,32]) as float64 numpy (test/diagnostic API).
-    ``virtual``: the pass also covers virtual.n_new SMOTE rows after ``rows``."""
+    ``virtual``: the pass also covers virtual.n_new SMOTE rows after ``rows``.
+    ``hess_stride``: the Hessian from every hess_stride-th tile of each wave; ``sub``: phase 0 of a
+    1/sub tile subset; ``hole``: (at, len) stored rows the pass steps over; ``nblocks``: the pass
+    grid (default: the resident grid); ``full``: return the whole reduced [1088] vector instead
+    (slot 34 is the weight behind H) -- ops/reference.py logreg_pass_tiles is its oracle."""
     check_rows(rows)
+    hs, sub = max(1, int(hess_stride)), max(1, int(sub))
+    rows, hole = _apply_hole(rows, hole)
     if not rows.is_cuda:
         R = ref.rows_to_f32(rows, fp8_scale).numpy()
-        return ref.logreg_pass(R, w.cpu().double().numpy(), class_w, hessian)
+        if not (full or hs > 1 or sub > 1):
+            return ref.logreg_pass(R, w.cpu().double().numpy(), class_w, hessian)
+        gw = ref.WAVES_PER_BLOCK * int(nblocks or 1024)  # the tile walk of a 1024-block grid by default
+        red = ref.logreg_pass_tiles(R, w.cpu().double().numpy(), class_w, hs, sub, 0, gw, bool(hessian))
+        if full:
+            return red
+        return red[:32].copy(), float(red[32]), float(red[33]), red[64:].reshape(32, 32) if hessian else None
     m = native()
-    ws = LRWorkspace(rows.device)
+    ws = LRWorkspace(rows.device, nblocks)
     ws.reset(w.cpu().double().numpy(), class_w)
-    n = rows.shape[0]
+    n = rows.shape[0] - hole[1]
     if virtual is not None:
         virtual.check(rows)
         virtual.prepare()
         n += virtual.n_new
-    _pass(m, rows, ws, hessian, 0, n, fp8_scale, stream_of(rows), done=False, virtual=virtual)
+    _pass(m, rows, ws, hs if hessian else 0, 0, n, fp8_scale, stream_of(rows), done=False, sub=sub, virtual=virtual,
+          hole=hole)
     red = ws.red.cpu().numpy()
+    if full:
+        return red
     H = red[64:].reshape(32, 32) if hessian else None
     return red[:32].copy(), float(red[32]), float(red[33]), H
+
+
+def newton_update_once(red, state, d: int = 30, C: float = 1.0, tol: float = 1e-8, max_iter: int = 25,
+                       fit_intercept: bool = True, phase_start: bool = False, affine=None, done: int = 0,
+                       w32=None, device=None):
+    """ONE launch of the Newton update kernel on a given reduced vector and state (test/diagnostic
+    API; ops/reference.py NewtonStateRef is its mirror).  ``red``: [1088] float64; ``state``: [256]
+    float64 (layout: the S_* offsets); ``affine``: [64] float64 (c | inv) or None; ``done``: the
+    done flag before the launch; ``w32``: [32] float32 the weight buffer holds before the launch
+    (default zeros).  Returns (state [256] float64, w32 [32] float32, done int) as numpy / int."""
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    red = np.ascontiguousarray(red, dtype=np.float64).reshape(-1)
+    state = np.ascontiguousarray(state, dtype=np.float64).reshape(-1)
+    if red.shape[0] != PART_STRIDE or state.shape[0] != STATE_SIZE:
+        raise ValueError("newton_update_once: red must be [1088] and state [256]")
+    ws = LRWorkspace(dev, 1)
+    ws.red.copy_(torch.from_numpy(red))
+    ws.state.copy_(torch.from_numpy(state))
+    if w32 is not None:
+        ws.w32.copy_(torch.from_numpy(np.ascontiguousarray(w32, dtype=np.float32).reshape(NCOLS)))
+    ws.done.fill_(int(done))
+    aff = None
+    if affine is not None:
+        aff = torch.from_numpy(np.ascontiguousarray(affine, dtype=np.float64).reshape(64)).to(dev)
+    native().newton_update(ptr(ws.red), ptr(ws.state), ptr(ws.w32), ptr(ws.done), int(d), float(C), float(tol),
+                           int(max_iter), int(fit_intercept), int(phase_start), ptr(aff) if aff is not None else 0,
+                           stream_of(ws.state))
+    return ws.state.cpu().numpy(), ws.w32.cpu().numpy(), int(ws.done.cpu()[0])
+
+
+def newton_iteration(rows: torch.Tensor, ws: LRWorkspace, hessian: int = 1, C: float = 1.0, tol: float = 0.0,
+                     max_iter: int = 1 << 30, d: int = 30, fit_intercept: bool = True, phase_start: bool = False,
+                     affine: torch.Tensor | None = None, fp8_scale: float = DEFAULT_FP8_SCALE, sub: int = 1):
+    """ONE Newton iteration on a prepared workspace (``ws.reset`` done by the caller): the pass
+    (``hessian``: 0 = gradient only, h >= 1 = Hessian stride) and the update behind it, in one launch
+    under FDX_NEWTON_FUSE=1 and as pass + logreg_reduce + newton_update otherwise -- exactly what
+    newton_fit enqueues per iteration (test/diagnostic API)."""
+    check_rows(rows)
+    upd = (ptr(affine) if affine is not None else 0, C, tol, d, max_iter, int(fit_intercept), int(phase_start), 0, 0)
+    _pass(native(), rows, ws, int(hessian), 0, rows.shape[0], fp8_scale, stream_of(rows), sub=sub, update=upd)
 
 
 def _apply_hole(rows: torch.Tensor, hole):

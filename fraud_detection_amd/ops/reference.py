@@ -226,6 +226,95 @@ def pack_reduced(g, loss, wsum, H) -> np.ndarray:
     return red
 
 
+def logreg_grad_abs(rows_f32: np.ndarray, w: np.ndarray, class_w=(1.0, 1.0)) -> np.ndarray:
+    """sum_i |r_i x_ij| per column: the absolute-term sum of logreg_pass's gradient, the scale an
+    accumulation error of the device pass is measured against (the loss's own terms are all
+    positive, so its absolute-term sum is the loss)."""
+    R = np.asarray(rows_f32, dtype=np.float64)
+    y = R[:, LABEL_COL].copy()
+    X = R.copy()
+    X[:, LABEL_COL] = 0.0
+    w = np.asarray(w, dtype=np.float64).copy()
+    w[LABEL_COL] = 0.0
+    s = np.where(y > 0.5, class_w[1], class_w[0])
+    r = s * (sigmoid(X @ w) - y)
+    return np.abs(X).T @ np.abs(r)
+
+
+def logreg_pass_tiles(rows_f32: np.ndarray, w: np.ndarray, class_w=(1.0, 1.0), hess_stride: int = 1, sub: int = 1,
+                      phase: int = 0, gw: int = 4096, hessian: bool = True) -> np.ndarray:
+    """The reduced [1088] vector of one device pass (logreg.hip bf16_wave_pass / fp8_wave_pass) over
+    the rows, with the pass's tile walk: rows come in tiles of ROW_TILE; the pass visits tile t iff
+    t mod sub == phase; the visited tiles are numbered j = t // sub and tile j is the i = j // gw-th
+    tile of wave j mod gw (gw = 4 waves x the grid's blocks).  That tile feeds the Hessian iff
+    (wave mod hess_stride + i) mod hess_stride == 0.  g, loss and red[33] cover every visited row;
+    H = hess_stride x the feeding tiles' Hessian and red[34] = hess_stride x their weight (the
+    Newton update rescales H by red[33] / red[34]).  ``hessian`` False: a gradient pass, H and
+    red[34] zero.  A CV hole is applied by deleting the block from the rows first."""
+    R = np.asarray(rows_f32, dtype=np.float64)
+    hs, sub, gw = int(hess_stride), int(sub), int(gw)
+    if hs < 1 or sub < 1 or gw < 1 or not 0 <= phase < sub:
+        raise ValueError("logreg_pass_tiles: hess_stride, sub, gw >= 1 and 0 <= phase < sub")
+    t = np.arange(R.shape[0], dtype=np.int64) // ROW_TILE
+    visited = t % sub == phase
+    j = t // sub
+    wave, i = j % gw, j // gw
+    g, loss, wsum, _ = logreg_pass(R[visited], w, class_w, hessian=False)
+    red = pack_reduced(g, loss, wsum, None)
+    if hessian:
+        feeds = visited & ((wave % hs + i) % hs == 0)
+        _, _, wh, H = logreg_pass(R[feeds], w, class_w, hessian=True)
+        red[34] = hs * wh
+        red[64:] = hs * np.asarray(H).reshape(-1)
+    return red
+
+
+def fold_weights(w: np.ndarray, affine: np.ndarray) -> np.ndarray:
+    """Standardized-space weights -> weights for pivot-shifted rows s with z = (s - c) inv
+    (logreg.hip store_folded; affine = c | inv): v_j = w_j inv_j, v_30 = w_30 - sum_j w_j inv_j c_j,
+    label slot 0.  fp64; the device stores it rounded to fp32."""
+    w = np.asarray(w, dtype=np.float64)
+    a = np.asarray(affine, dtype=np.float64)
+    c, inv = a[:32], a[32:]
+    v = w * inv
+    v[BIAS_COL] = w[BIAS_COL] - float(np.sum(w * inv * c))
+    v[LABEL_COL] = 0.0
+    return v
+
+
+def newton_system(red, w, d, C, fit_intercept=True, affine=None):
+    """(idx, A, grad, obj, gmax) of one Newton update from the reduced vector: the active
+    coordinates, the matrix A = H[idx, idx] / S_H + reg I_pen the update factors, the gradient and
+    objective of sklearn's loss at ``w``, and the gradient's max norm over idx.  ``affine`` (c | inv,
+    [64]): the sums were taken over pivot-shifted rows s, z = (s - c) inv, and map to standardized
+    space first: g_z[j] = inv_j (g_j - c_j g_30),
+    H_z[j][k] = inv_j inv_k (H_jk - c_j H_30k - c_k H_j30 + c_j c_k H_30,30)."""
+    red = np.asarray(red, dtype=np.float64)
+    g = red[:32]
+    Hf = red[64:].reshape(32, 32)
+    if affine is not None:
+        a = np.asarray(affine, dtype=np.float64)
+        c, inv = a[:32], a[32:]
+        g = inv * (g - c * g[BIAS_COL])
+        Hf = np.outer(inv, inv) * (Hf - np.outer(c, Hf[BIAS_COL, :]) - np.outer(Hf[:, BIAS_COL], c)
+                                   + np.outer(c, c) * Hf[BIAS_COL, BIAS_COL])
+    S = red[33] if red[33] > 0 else 1.0
+    reg = 1.0 / (C * S)
+    idx = list(range(d)) + ([BIAS_COL] if fit_intercept else [])
+    grad = np.zeros(32)
+    grad[:d] = g[:d] / S + reg * w[:d]
+    if fit_intercept:
+        grad[BIAS_COL] = g[BIAS_COL] / S
+    obj = red[32] / S + 0.5 * reg * float(np.dot(w[:d], w[:d]))
+    gmax = float(np.max(np.abs(grad[idx])))
+    SH = red[34] if red[34] > 0 else S  # weight of the rows behind H (device: slot 34)
+    A = Hf[np.ix_(idx, idx)] / SH
+    for k, j in enumerate(idx):
+        if j < d:
+            A[k, k] += reg
+    return idx, A, grad, obj, gmax
+
+
 class NewtonStateRef:
     """Mirror of logreg.hip newton_update_kernel (same decisions, fp64)."""
 
@@ -243,23 +332,20 @@ class NewtonStateRef:
         self.converged = False
         self.done = False
 
-    def update(self, red, d, C, tol, max_iter, fit_intercept=True):
+    def update(self, red, d, C, tol, max_iter, fit_intercept=True, phase_start=False, affine=None):
+        """``phase_start``: first iteration of a progressive-Newton phase -- the previous objective
+        counts as +inf and the backtrack count as 0 (objectives of different row samples are not
+        comparable).  ``affine``: see newton_system."""
         if self.done:
             return
-        S = red[33] if red[33] > 0 else 1.0
-        reg = 1.0 / (C * S)
-        idx = list(range(d)) + ([BIAS_COL] if fit_intercept else [])
-        grad = np.zeros(32)
-        grad[:d] = red[:d] / S + reg * self.w[:d]
-        if fit_intercept:
-            grad[BIAS_COL] = red[BIAS_COL] / S
-        obj = red[32] / S + 0.5 * reg * float(np.dot(self.w[:d], self.w[:d]))
-        gmax = float(np.max(np.abs(grad[idx])))
+        idx, A, grad, obj, gmax = newton_system(red, self.w, d, C, fit_intercept, affine)
+        prev = np.inf if phase_start else self.obj_prev
+        nbt = 0 if phase_start else self.backtracks
         self.obj = obj
-        if self.iter > 0 and obj > self.obj_prev + 1e-6 * abs(self.obj_prev) and self.backtracks < 40:
+        if self.iter > 0 and obj > prev + 1e-6 * abs(prev) and nbt < 40:
             self.step *= 0.5
             self.w = self.w_prev + self.step
-            self.backtracks += 1
+            self.backtracks = nbt + 1
             dec = 1
         elif gmax <= tol:
             self.gmax = gmax
@@ -268,12 +354,6 @@ class NewtonStateRef:
             dec = 2
         else:
             self.gmax = gmax
-            Hf = np.asarray(red[64:]).reshape(32, 32)
-            SH = red[34] if red[34] > 0 else S  # weight of the rows behind H (device: slot 34)
-            A = Hf[np.ix_(idx, idx)] / SH
-            for k, j in enumerate(idx):
-                if j < d:
-                    A[k, k] += reg
             L = np.linalg.cholesky(A)
             st = np.linalg.solve(L.T, np.linalg.solve(L, -grad[idx]))
             self.w_prev = self.w.copy()
