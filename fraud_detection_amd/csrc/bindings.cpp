@@ -911,9 +911,11 @@ PYBIND11_MODULE(_fdx_native, m) {
   });
 
   // gbdt (K11)
-  m.def("gbdt_bin", [](u X, int64_t n, int ld, int d, u cuts, u nbins, u bins, u s) {
-    fdx::launch_gbdt_bin(P<const float>(X), n, ld, d, P<const float>(cuts), P<const int>(nbins), P<uint8_t>(bins), S(s));
-  });
+  m.def("gbdt_bin", [](u X, int64_t n, int ld, int d, u cuts, u nbins, u bins, u s, bool missing) {
+    fdx::launch_gbdt_bin(P<const float>(X), n, ld, d, P<const float>(cuts), P<const int>(nbins), P<uint8_t>(bins), S(s),
+                         missing);
+  }, py::arg("X"), py::arg("n"), py::arg("ld"), py::arg("d"), py::arg("cuts"), py::arg("nbins"), py::arg("bins"),
+     py::arg("s"), py::arg("missing") = false);
   m.def("gbdt_grad", [](u margin, u label, int64_t n, float spw, float gscale, float hscale, u gh, u s) {
     fdx::launch_gbdt_grad(P<const float>(margin), P<const uint8_t>(label), n, spw, gscale, hscale, P<uint32_t>(gh), S(s));
   });
@@ -924,9 +926,12 @@ PYBIND11_MODULE(_fdx_native, m) {
   });
   m.def("gbdt_hist_blocks", [] { return fdx::gbdt_hist_blocks(); });
   m.def("quantile_select_ws_bytes", [](int64_t m, int d) { return fdx::quantile_select_ws_bytes(m, d); });
-  m.def("quantile_select", [](u X, int64_t m, int64_t stride, int ld, int d, int max_bin, u ws, u out, u s) {
-    fdx::launch_quantile_select(P<const float>(X), m, stride, ld, d, max_bin, P<void>(ws), P<float>(out), S(s));
-  });
+  m.def("quantile_select", [](u X, int64_t m, int64_t stride, int ld, int d, int max_bin, u ws, u out, u s,
+                              u counts) {
+    fdx::launch_quantile_select(P<const float>(X), m, stride, ld, d, max_bin, P<void>(ws), P<float>(out), S(s),
+                                P<const int64_t>(counts));
+  }, py::arg("X"), py::arg("m"), py::arg("stride"), py::arg("ld"), py::arg("d"), py::arg("max_bin"), py::arg("ws"),
+     py::arg("out"), py::arg("s"), py::arg("counts") = 0);
   m.def("gbdt_hist_slot_words", [] { return fdx::gbdt_hist_slot_words(); });
   m.def("set_gbdt_hist_variant", [](int v) { fdx::set_gbdt_hist_variant(v); });
   m.def("gbdt_hist", [](u bins, u gh, u ridx, u seg, u gcnt, int level, int d, u hist, u slots, u s,
@@ -947,14 +952,16 @@ PYBIND11_MODULE(_fdx_native, m) {
                                    hscale);
   });
   m.def("gbdt_split", [](u hist, u gcnt, int level, int d, u nbins, u cuts, double ginv, double hinv, double lam,
-                         double mcw, double gamma, u feat, u bin, u thr, u gain, u ng, u nh, u s, u fmask) {
+                         double mcw, double gamma, u feat, u bin, u thr, u gain, u ng, u nh, u s, u fmask,
+                         bool missing) {
     fdx::launch_gbdt_split(P<unsigned long long>(hist), P<const int64_t>(gcnt), level, d, P<const int>(nbins),
                            P<const float>(cuts), ginv, hinv, lam, mcw, gamma, P<int>(feat), P<int>(bin), P<float>(thr),
-                           P<double>(gain), P<long long>(ng), P<long long>(nh), S(s), P<const uint32_t>(fmask));
+                           P<double>(gain), P<long long>(ng), P<long long>(nh), S(s), P<const uint32_t>(fmask),
+                           missing);
   }, py::arg("hist"), py::arg("gcnt"), py::arg("level"), py::arg("d"), py::arg("nbins"), py::arg("cuts"),
      py::arg("ginv"), py::arg("hinv"), py::arg("lam"), py::arg("mcw"), py::arg("gamma"), py::arg("feat"),
      py::arg("bin"), py::arg("thr"), py::arg("gain"), py::arg("ng"), py::arg("nh"), py::arg("s"),
-     py::arg("fmask") = 0);
+     py::arg("fmask") = 0, py::arg("missing") = false);
   m.def("gbdt_transpose", [](u bins, int64_t n, int d, u binsT, int64_t ldt, u s) {
     fdx::launch_gbdt_transpose(P<const uint8_t>(bins), n, d, P<uint8_t>(binsT), ldt, S(s));
   });
@@ -1044,10 +1051,11 @@ PYBIND11_MODULE(_fdx_native, m) {
                                         P<const float>(weight), wscale, P<long long>(rec), S(s));
   });
   m.def("gbdt_predict", [](u X, int64_t n, int ld, int d, u feat, u thr, u leaf, int ntrees, int depth, float base,
-                           u out, u s) {
+                           u out, u s, u dleft) {
     fdx::launch_gbdt_predict(P<const float>(X), n, ld, d, P<const int>(feat), P<const float>(thr), P<const float>(leaf),
-                             ntrees, depth, base, P<float>(out), S(s));
-  });
+                             ntrees, depth, base, P<float>(out), S(s), P<const uint8_t>(dleft));
+  }, py::arg("X"), py::arg("n"), py::arg("ld"), py::arg("d"), py::arg("feat"), py::arg("thr"), py::arg("leaf"),
+     py::arg("ntrees"), py::arg("depth"), py::arg("base"), py::arg("out"), py::arg("s"), py::arg("dleft") = 0);
 
   // auc / confusion
   m.def("auc_hist", [](u scores, u labels, int64_t n, int bits, u hist, u s) {

@@ -75,8 +75,12 @@ __device__ __forceinline__ bool is_built(int node, const int64_t* gcnt) {
 //  * the first three search levels compare against registers (7 cuts per feature), the last five
 //    read LDS.
 // (2.78 ms in round 3; 0.94 ms with the vector loads and the LDS-only search, profiles/r4_k)
+//  * MISS (missing_policy "learn"): a NaN of either sign takes byte 255, the missing slot, whatever
+//    the feature's bin count (the cuts then hold at most 255 real bins); every other value is
+//    searched and clamped as without the flag.
 constexpr int kCutLd = 33;
-template <bool VEC>
+constexpr int kMissingBin = 255;
+template <bool VEC, bool MISS = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void gbdt_bin_kernel(const float* __restrict__ X, int64_t n, int ld,
                                                        int d, const float* __restrict__ cuts,
                                                        const int* __restrict__ nbins,
@@ -148,7 +152,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void g
     uint32_t packed = 0;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const int bb = (sub * 4 + j < d) ? min(b[j], nbm1[j]) : 0;
+      int bb = (sub * 4 + j < d) ? min(b[j], nbm1[j]) : 0;
+      if constexpr (MISS) bb = (sub * 4 + j < d && x[j] != x[j]) ? kMissingBin : bb;
       packed |= (uint32_t)bb << (8 * j);
     }
     reinterpret_cast<uint32_t*>(bins + r * kGBRowBytes)[sub] = packed;
@@ -746,6 +751,15 @@ struct SplitOut {
   long long* ch;
 };
 
+// MISS (missing_policy "learn"): bin slot 255 of every feature holds the missing rows' sums (Gm, Hm)
+// and the scan learns their side.  A feature's candidates, in tie order: b = -1 with default left
+// (left = the missing rows alone); then for b = 0 .. nbins - 2 "missing right" (GL = prefix(b)) and
+// "missing left" (GL = prefix(b) + Gm).  A candidate's key is 2 (b + 1) + default_left -- ties go to
+// the lowest key -- and takes the place of the bin in the argmax; without MISS the key is b itself.
+// Same gain arithmetic and validity tests.  The node's `bin` gets the walk's word: b for a
+// missing-right split, 0x200 | (b + 1) for a default-left one (goes_right); thr of b = -1 is -inf,
+// so x < thr is false for every non-NaN x and the fp32 walk agrees with the binned one.
+template <bool MISS>
 __global__ __launch_bounds__(kHistThreads) void gbdt_split_kernel(
     unsigned long long* __restrict__ hist, const int64_t* __restrict__ gcnt, int level, int d,
     const int* __restrict__ nbins, const float* __restrict__ cuts, double ginv, double hinv,
@@ -790,6 +804,8 @@ __global__ __launch_bounds__(kHistThreads) void gbdt_split_kernel(
         h[j] = H[e0 + 2 * j + 1];
       }
     }
+    [[maybe_unused]] long long Gm = 0, Hm = 0;  // MISS: slot 255 = lane 63's fourth bin
+    if constexpr (MISS) { Gm = __shfl(g[3], 63, kWave); Hm = __shfl(h[3], 63, kWave); }
 #pragma unroll
     for (int j = 1; j < 4; ++j) { g[j] += g[j - 1]; h[j] += h[j - 1]; }
     long long eg = g[3], eh = h[3];  // inclusive scan of lane totals
@@ -809,16 +825,27 @@ __global__ __launch_bounds__(kHistThreads) void gbdt_split_kernel(
     double best = -1.0e300;
     int bb = 0x7fffffff;
     long long bgl = 0, bhl = 0;
+    // one candidate: left sums (GLq, HLq) under key `key`; tried in ascending key order per lane
+    auto consider = [&](bool in_range, int key, long long GLq, long long HLq) {
+#pragma clang fp contract(off)
+      const double GL = (double)GLq * ginv, HL = (double)HLq * hinv;
+      const double GR = (double)(Gq - GLq) * ginv, HR = (double)(Hq - HLq) * hinv;
+      if (in_range && HL >= min_child_weight && HR >= min_child_weight) {
+        const double dl = HL + lambda, dr = HR + lambda;
+        const double gain = ((dl > 0.0 ? GL * GL / dl : 0.0) + (dr > 0.0 ? GR * GR / dr : 0.0)) - root;
+        if (gain > best) { best = gain; bb = key; bgl = GLq; bhl = HLq; }
+      }
+    };
+    if constexpr (MISS) consider(lane == 0, 1, Gm, Hm);  // b = -1: the missing rows alone go left
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int b = lane * 4 + j;
       const long long GLq = pg + g[j], HLq = ph + h[j];
-      const double GL = (double)GLq * ginv, HL = (double)HLq * hinv;
-      const double GR = (double)(Gq - GLq) * ginv, HR = (double)(Hq - HLq) * hinv;
-      if (b < nb - 1 && HL >= min_child_weight && HR >= min_child_weight) {
-        const double dl = HL + lambda, dr = HR + lambda;
-        const double gain = ((dl > 0.0 ? GL * GL / dl : 0.0) + (dr > 0.0 ? GR * GR / dr : 0.0)) - root;
-        if (gain > best) { best = gain; bb = b; bgl = GLq; bhl = HLq; }
+      if constexpr (MISS) {
+        consider(b < nb - 1, 2 * (b + 1), GLq, HLq);
+        consider(b < nb - 1, 2 * (b + 1) + 1, GLq + Gm, HLq + Hm);
+      } else {
+        consider(b < nb - 1, b, GLq, HLq);
       }
     }
 #pragma unroll
@@ -848,8 +875,14 @@ __global__ __launch_bounds__(kHistThreads) void gbdt_split_kernel(
     const int l = 2 * node + 1, r = 2 * node + 2;
     if (split) {
       tfeat[node] = bf;
-      tbin[node] = fbin[bf];
-      tthr[node] = cuts[bf * kGBBins + fbin[bf]];
+      if constexpr (MISS) {
+        const int key = fbin[bf], b = (key >> 1) - 1;
+        tbin[node] = (key & 1) ? (0x200 | (b + 1)) : b;
+        tthr[node] = b < 0 ? -__builtin_inff() : cuts[bf * kGBBins + b];
+      } else {
+        tbin[node] = fbin[bf];
+        tthr[node] = cuts[bf * kGBBins + fbin[bf]];
+      }
       tgain[node] = best;
       ng[l] = fgl[bf]; nh[l] = fhl[bf];
       ng[r] = Gq - fgl[bf]; nh[r] = Hq - fhl[bf];
@@ -875,10 +908,20 @@ __device__ __forceinline__ void part_range(int64_t n, int64_t* lo, int64_t* hi) 
 // binsT: FEATURE-major u8 bins [d][ldt].  The partition reads one feature byte per row: from the
 // row-major [n][32] layout every such byte costs a whole sector (~205 MB of traffic per level at
 // 6.4M rows); a feature column is 1 B/row and stays L2 / Infinity Cache resident.
+// The node's `bin` is a split word.  A word in [0x200, 0x3ff] is a default-left split of bin b,
+// 0x200 | (b + 1); every other word is the split bin itself and means what it always did, v > w
+// (a missing row, byte 255, goes right like every byte above the bin; -1 sends every row right).
+// With s = (w in [0x200, 0x3ff]) and c = w - (s << 9) a byte v goes right iff ((v + s) & 0xff) > c:
+// for the new words byte 255 wraps to 0 and goes left, every other byte compares v + 1 > b + 1, and
+// b = -1 (the missing rows alone go left) needs no case of its own.
+__device__ __forceinline__ bool word_right(int v, int w) {
+  const int s = ((unsigned)w >> 9) == 1u ? 1 : 0;
+  return ((v + s) & 0xff) > w - (s << 9);
+}
 __device__ __forceinline__ bool goes_right(const uint8_t* binsT, int64_t ldt, int64_t row, int node,
                                            const int* feat, const int* bin) {
   const int f = feat[node];
-  return f >= 0 && binsT[(int64_t)f * ldt + row] > bin[node];
+  return f >= 0 && word_right((int)binsT[(int64_t)f * ldt + row], bin[node]);
 }
 
 // Row-major [n][32] -> feature-major [d][ldt] (ldt % 4 == 0): a 256-row tile through LDS, each
@@ -976,7 +1019,7 @@ __global__ __launch_bounds__(kPartThreads) void gbdt_part_count_kernel(
 #pragma unroll
     for (int u = 0; u < kPartRows; ++u) {
       if (p0 + u < hi) {
-        const int r = f[u] >= 0 && (int)v[u] > bv[u];
+        const int r = f[u] >= 0 && word_right((int)v[u], bv[u]);
         flag[p0 + u] = (uint8_t)r;
         c += r;
         if (nd[u] != cn) {
@@ -1357,10 +1400,14 @@ __global__ __launch_bounds__(kEvalThreads) void gbdt_eval_kernel(
 constexpr int kPredThreads = 256;
 constexpr int kPredLdsFloats = 12288;  // 48 KiB of trees per chunk
 
+// dleft (u8 [ntrees][ni], null: none set): a NaN goes LEFT at a node whose byte is set, right
+// otherwise as it always did (!(NaN < thr) holds).  The byte rides in bit 8 of the node's LDS feat
+// word (features are < 30), so the per-tree LDS footprint and the chunk size are unchanged.
+constexpr int kPredDefaultLeft = 0x100;
 __global__ __launch_bounds__(kPredThreads) void gbdt_predict_kernel(
     const float* __restrict__ X, int64_t n, int ld, int d, const int* __restrict__ feat,
     const float* __restrict__ thr, const float* __restrict__ leaf, int ntrees, int depth,
-    float base_margin, float* __restrict__ out) {
+    float base_margin, float* __restrict__ out, const uint8_t* __restrict__ dleft) {
   __shared__ float xr[kPredThreads][kGBMaxFeat + 1];
   __shared__ float tl[kPredLdsFloats];
   const int ni = (1 << depth) - 1, nl = 1 << depth;
@@ -1375,7 +1422,9 @@ __global__ __launch_bounds__(kPredThreads) void gbdt_predict_kernel(
     __syncthreads();
     for (int i = threadIdx.x; i < nt * ni; i += kPredThreads) {
       const int t = i / ni, k = i % ni;
-      tl[t * per_tree + k] = __int_as_float(feat[(int64_t)(t0 + t) * ni + k]);
+      int fw = feat[(int64_t)(t0 + t) * ni + k];
+      if (dleft != nullptr && fw >= 0 && dleft[(int64_t)(t0 + t) * ni + k] != 0) fw |= kPredDefaultLeft;
+      tl[t * per_tree + k] = __int_as_float(fw);
       tl[t * per_tree + ni + k] = thr[(int64_t)(t0 + t) * ni + k];
     }
     for (int i = threadIdx.x; i < nt * nl; i += kPredThreads) {
@@ -1387,8 +1436,12 @@ __global__ __launch_bounds__(kPredThreads) void gbdt_predict_kernel(
       const float* T = tl + t * per_tree;
       int node = 0;
       for (int l = 0; l < depth; ++l) {
-        const int f = __float_as_int(T[node]);
-        const bool right = f >= 0 && !(xr[threadIdx.x][f] < T[ni + node]);
+        const int fw = __float_as_int(T[node]);
+        bool right = false;
+        if (fw >= 0) {
+          const float x = xr[threadIdx.x][fw & 0xff];
+          right = !(x < T[ni + node]) && !(x != x && (fw & kPredDefaultLeft) != 0);
+        }
         node = 2 * node + 1 + (right ? 1 : 0);
       }
       acc += T[2 * ni + node - ni];
@@ -1399,13 +1452,23 @@ __global__ __launch_bounds__(kPredThreads) void gbdt_predict_kernel(
 
 }  // namespace
 
+template <bool VEC, bool MISS>
+static void run_gbdt_bin(const float* X, int64_t n, int ld, int d, const float* cuts, const int* nbins,
+                         uint8_t* bins, hipStream_t stream) {
+  static const int cap = resident_cap(gbdt_bin_kernel<VEC, MISS>, 256);
+  gbdt_bin_kernel<VEC, MISS><<<capped_grid(n, 256 / 8, cap), 256, 0, stream>>>(X, n, ld, d, cuts, nbins, bins);
+}
+
 void launch_gbdt_bin(const float* X, int64_t n, int ld, int d, const float* cuts, const int* nbins,
-                     uint8_t* bins, hipStream_t stream) {
+                     uint8_t* bins, hipStream_t stream, bool missing) {
   if (d > kGBMaxFeat) throw std::runtime_error("gbdt: at most 30 features");
   // VEC loads float4 columns 0..31 of every row whatever d is, so a row must own 32 floats (the
   // pipeline's [n, 32] rows): with a narrower ld the last rows' loads would run past the table
   const bool vec = ld >= 32 && (ld % 4) == 0 && (reinterpret_cast<uintptr_t>(X) % 16) == 0;
-  if (vec) {
+  if (missing) {  // both load paths
+    if (vec) run_gbdt_bin<true, true>(X, n, ld, d, cuts, nbins, bins, stream);
+    else run_gbdt_bin<false, true>(X, n, ld, d, cuts, nbins, bins, stream);
+  } else if (vec) {
     static const int cap = resident_cap(gbdt_bin_kernel<true>, 256);
     gbdt_bin_kernel<true><<<capped_grid(n, 256 / 8, cap), 256, 0, stream>>>(X, n, ld, d, cuts, nbins, bins);
   } else {
@@ -1550,10 +1613,18 @@ void launch_gbdt_hist_l0_fused(const uint8_t* bins, uint32_t* gh, const int64_t*
 void launch_gbdt_split(unsigned long long* hist, const int64_t* gcnt, int level, int d, const int* nbins,
                        const float* cuts, double ginv, double hinv, double lambda,
                        double min_child_weight, double gamma, int* feat, int* bin, float* thr,
-                       double* gain, long long* ng, long long* nh, hipStream_t stream, const uint32_t* fmask) {
-  gbdt_split_kernel<<<1 << level, kHistThreads, 0, stream>>>(hist, gcnt, level, d, nbins, cuts, ginv, hinv,
-                                                             lambda, min_child_weight, gamma, feat, bin,
-                                                             thr, gain, ng, nh, fmask);
+                       double* gain, long long* ng, long long* nh, hipStream_t stream, const uint32_t* fmask,
+                       bool missing) {
+  if (level < 0 || (1 << level) > kGBMaxNodes + 1) throw std::runtime_error("gbdt_split: level out of range");
+  if (d < 1 || d > kGBMaxFeat) throw std::runtime_error("gbdt_split: bad feature count");
+  if (missing)
+    gbdt_split_kernel<true><<<1 << level, kHistThreads, 0, stream>>>(hist, gcnt, level, d, nbins, cuts, ginv, hinv,
+                                                                     lambda, min_child_weight, gamma, feat, bin,
+                                                                     thr, gain, ng, nh, fmask);
+  else
+    gbdt_split_kernel<false><<<1 << level, kHistThreads, 0, stream>>>(hist, gcnt, level, d, nbins, cuts, ginv, hinv,
+                                                                      lambda, min_child_weight, gamma, feat, bin,
+                                                                      thr, gain, ng, nh, fmask);
   check_launch("gbdt_split");
 }
 
@@ -1711,13 +1782,13 @@ void launch_gbdt_eval_walk_weighted(const uint8_t* binsT, int64_t ldt, int64_t n
 
 void launch_gbdt_predict(const float* X, int64_t n, int ld, int d, const int* feat, const float* thr,
                          const float* leaf, int ntrees, int depth, float base_margin, float* out,
-                         hipStream_t stream) {
+                         hipStream_t stream, const uint8_t* dleft) {
   if (depth < 1 || depth > 8) throw std::runtime_error("gbdt: depth must be in [1, 8]");
   if (d > kGBMaxFeat) throw std::runtime_error("gbdt: at most 30 features");
   const int64_t grid = (n + kPredThreads - 1) / kPredThreads;
   if (grid == 0) return;
   gbdt_predict_kernel<<<(unsigned)grid, kPredThreads, 0, stream>>>(X, n, ld, d, feat, thr, leaf, ntrees, depth,
-                                                                   base_margin, out);
+                                                                   base_margin, out, dleft);
   check_launch("gbdt_predict");
 }
 

@@ -1,0 +1,142 @@
+// Host-side self-test of the GBDT launchers whose signatures grew for missing_policy="learn"
+// (gbdt.hip launch_gbdt_bin / launch_gbdt_split / launch_gbdt_predict, quantile.hip
+// launch_quantile_select): every argument check must throw BEFORE anything is launched, whatever the
+// new trailing arguments are, and the old call forms (trailing arguments left out) must still
+// compile.  Built with -fsanitize=address,undefined on the host side (tools/sanitize_host.sh); it
+// needs no GPU: a call that passes its checks either launches or reports the missing device as a
+// std::runtime_error from check_launch, and both count as "got past the checks".
+#include <cstdint>
+#include <cstdio>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "launchers.h"
+
+namespace {
+
+int failures = 0;
+
+template <typename F>
+void expect_refused(const char* what, const char* needle, F&& f) {
+  try {
+    f();
+  } catch (const std::exception& e) {
+    if (std::string(e.what()).find(needle) != std::string::npos) return;
+    std::printf("FAIL %s: refused with an unexpected message: %s\n", what, e.what());
+    ++failures;
+    return;
+  }
+  std::printf("FAIL %s: not refused\n", what);
+  ++failures;
+}
+
+// Past the checks: a launch, or the runtime's own error where there is no device.
+template <typename F>
+void expect_checked(const char* what, F&& f) {
+  try {
+    f();
+  } catch (const std::runtime_error& e) {
+    if (std::string(e.what()).find("fdx kernel launch failed") != std::string::npos ||
+        std::string(e.what()).find("memset failed") != std::string::npos)
+      return;
+    std::printf("FAIL %s: refused a valid call: %s\n", what, e.what());
+    ++failures;
+  }
+}
+
+}  // namespace
+
+int main() {
+  int ndev = 0;
+  const bool have_gpu = hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0;
+  // host buffers stand in for device memory: with a GPU present nothing valid is launched on them
+  std::vector<float> f32(64 * 32, 0.0f);
+  std::vector<int> i32(256, 1);
+  std::vector<uint8_t> u8(64 * 32, 0);
+  std::vector<long long> i64(256, 0);
+  std::vector<int64_t> gc(256, 0);
+  std::vector<double> f64(256, 0.0);
+  std::vector<unsigned long long> hist(16, 0);
+  const int64_t counts[32] = {0};
+
+  for (bool missing : {false, true}) {
+    expect_refused("gbdt_bin d = 31", "at most 30 features", [&] {
+      fdx::launch_gbdt_bin(f32.data(), 1, 31, 31, f32.data(), i32.data(), u8.data(), nullptr, missing);
+    });
+    expect_refused("gbdt_split level = -1", "level out of range", [&] {
+      fdx::launch_gbdt_split(hist.data(), gc.data(), -1, 4, i32.data(), f32.data(), 1.0, 1.0, 1.0, 1.0, 0.0, i32.data(),
+                             i32.data(), f32.data(), f64.data(), i64.data(), i64.data(), nullptr, nullptr, missing);
+    });
+    expect_refused("gbdt_split level = 8", "level out of range", [&] {
+      fdx::launch_gbdt_split(hist.data(), gc.data(), 8, 4, i32.data(), f32.data(), 1.0, 1.0, 1.0, 1.0, 0.0, i32.data(),
+                             i32.data(), f32.data(), f64.data(), i64.data(), i64.data(), nullptr, nullptr, missing);
+    });
+    for (int d : {0, 31})
+      expect_refused("gbdt_split bad d", "bad feature count", [&] {
+        fdx::launch_gbdt_split(hist.data(), gc.data(), 0, d, i32.data(), f32.data(), 1.0, 1.0, 1.0, 1.0, 0.0,
+                               i32.data(), i32.data(), f32.data(), f64.data(), i64.data(), i64.data(), nullptr, nullptr,
+                               missing);
+      });
+  }
+  for (const uint8_t* dleft : {static_cast<const uint8_t*>(nullptr), static_cast<const uint8_t*>(u8.data())}) {
+    for (int depth : {0, 9})
+      expect_refused("gbdt_predict bad depth", "depth must be in [1, 8]", [&] {
+        fdx::launch_gbdt_predict(f32.data(), 1, 30, 30, i32.data(), f32.data(), f32.data(), 1, depth, 0.0f, f32.data(),
+                                 nullptr, dleft);
+      });
+    expect_refused("gbdt_predict d = 31", "at most 30 features", [&] {
+      fdx::launch_gbdt_predict(f32.data(), 1, 31, 31, i32.data(), f32.data(), f32.data(), 1, 3, 0.0f, f32.data(), nullptr,
+                               dleft);
+    });
+    // no rows: returns before any launch, with or without the bytes
+    fdx::launch_gbdt_predict(f32.data(), 0, 30, 30, i32.data(), f32.data(), f32.data(), 1, 3, 0.0f, f32.data(), nullptr,
+                             dleft);
+  }
+  for (const int64_t* c : {static_cast<const int64_t*>(nullptr), counts}) {
+    expect_refused("quantile_select d = 0", "quantile_select: need", [&] {
+      fdx::launch_quantile_select(f32.data(), 8, 1, 4, 0, 16, f32.data(), f32.data(), nullptr, c);
+    });
+    expect_refused("quantile_select d = 33", "quantile_select: need", [&] {
+      fdx::launch_quantile_select(f32.data(), 8, 1, 33, 33, 16, f32.data(), f32.data(), nullptr, c);
+    });
+    expect_refused("quantile_select max_bin = 1", "quantile_select: need", [&] {
+      fdx::launch_quantile_select(f32.data(), 8, 1, 4, 4, 1, f32.data(), f32.data(), nullptr, c);
+    });
+    expect_refused("quantile_select max_bin = 257", "quantile_select: need", [&] {
+      fdx::launch_quantile_select(f32.data(), 8, 1, 4, 4, 257, f32.data(), f32.data(), nullptr, c);
+    });
+    expect_refused("quantile_select m = 0", "quantile_select: need", [&] {
+      fdx::launch_quantile_select(f32.data(), 0, 1, 4, 4, 16, f32.data(), f32.data(), nullptr, c);
+    });
+    expect_refused("quantile_select m = 2^31", "at most 2^31 - 1", [&] {
+      fdx::launch_quantile_select(f32.data(), (int64_t)1 << 31, 1, 4, 4, 16, f32.data(), f32.data(), nullptr, c);
+    });
+  }
+  // the call forms from before the trailing arguments existed still compile, and reach the same checks
+  expect_refused("gbdt_bin, old form", "at most 30 features", [&] {
+    fdx::launch_gbdt_bin(f32.data(), 1, 31, 31, f32.data(), i32.data(), u8.data(), nullptr);
+  });
+  expect_refused("gbdt_split, old form", "level out of range", [&] {
+    fdx::launch_gbdt_split(hist.data(), gc.data(), -1, 4, i32.data(), f32.data(), 1.0, 1.0, 1.0, 1.0, 0.0, i32.data(),
+                           i32.data(), f32.data(), f64.data(), i64.data(), i64.data(), nullptr);
+  });
+  expect_refused("gbdt_predict, old form", "depth must be in [1, 8]", [&] {
+    fdx::launch_gbdt_predict(f32.data(), 1, 30, 30, i32.data(), f32.data(), f32.data(), 1, 0, 0.0f, f32.data(), nullptr);
+  });
+  expect_refused("quantile_select, old form", "quantile_select: need", [&] {
+    fdx::launch_quantile_select(f32.data(), 0, 1, 4, 4, 16, f32.data(), f32.data(), nullptr);
+  });
+  if (!have_gpu) {  // valid arguments without a device: past the checks, then the runtime's error
+    for (bool missing : {false, true})
+      expect_checked("gbdt_bin, valid", [&] {
+        fdx::launch_gbdt_bin(f32.data(), 4, 32, 30, f32.data(), i32.data(), u8.data(), nullptr, missing);
+      });
+  }
+  if (failures) {
+    std::printf("gbdt_args_selftest: %d failure(s)\n", failures);
+    return 1;
+  }
+  std::printf("gbdt_args_selftest: ok (%s)\n", have_gpu ? "GPU present: argument checks only" : "no GPU");
+  return 0;
+}

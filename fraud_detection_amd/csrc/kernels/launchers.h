@@ -430,8 +430,9 @@ void launch_kernelshap_tree(const float* Xs, int ldx, int n_expl, int d, const i
                             float* f0_out, float* ws, unsigned* cnt, hipStream_t stream);
 
 // ---- K11 gbdt (gbdt.hip) ----
+// missing: a NaN takes byte 255, the missing slot (missing_policy "learn"; nbins <= 255 then)
 void launch_gbdt_bin(const float* X, int64_t n, int ld, int d, const float* cuts, const int* nbins,
-                     uint8_t* bins, hipStream_t stream);
+                     uint8_t* bins, hipStream_t stream, bool missing = false);
 void launch_gbdt_grad(const float* margin, const uint8_t* label, int64_t n, float spw, float gscale,
                       float hscale, uint32_t* gh, hipStream_t stream);
 // Row subsampling: table row r of round `round` keeps its gradients iff its Philox word (seed,
@@ -444,8 +445,9 @@ int gbdt_hist_blocks();
 // exact per-feature order statistics of the cut sample (quantile.hip): out [max_bin][d] holds the
 // minimum (row 0) and the values at ranks floor(t m / max_bin); rows r * stride of X [., ld]
 int64_t quantile_select_ws_bytes(int64_t m, int d);
+// counts: device int64 [d] per-feature rank bases (the non-NaN counts); null: m for every feature
 void launch_quantile_select(const float* X, int64_t m, int64_t stride, int ld, int d, int max_bin, void* ws,
-                            float* out, hipStream_t stream);
+                            float* out, hipStream_t stream, const int64_t* counts = nullptr);
 int64_t gbdt_hist_slot_words();  // int64 words of the per-(node, block) histogram slots
 // hole_at / hole_len (hist and partition): the fit's rows are the table minus the block
 // [hole_at, hole_at + hole_len) -- a cross-validation fold on the fold-sorted table (n counts the
@@ -465,7 +467,8 @@ void launch_gbdt_split(unsigned long long* hist, const int64_t* gcnt, int level,
                        const float* cuts, double ginv, double hinv, double lambda,
                        double min_child_weight, double gamma, int* feat, int* bin, float* thr,
                        double* gain, long long* ng, long long* nh, hipStream_t stream,
-                       const uint32_t* fmask = nullptr);  // [heap] allowed-feature bits per node; null: all
+                       const uint32_t* fmask = nullptr,  // [heap] allowed-feature bits per node; null: all
+                       bool missing = false);  // slot 255 = the missing rows; `bin` gets split words (gbdt.hip)
 // row-major [n][32] bins -> feature-major [d][ldt] (the partition's per-row feature reads)
 void launch_gbdt_transpose(const uint8_t* bins, int64_t n, int d, uint8_t* binsT, int64_t ldt, hipStream_t stream);
 void launch_gbdt_partition(const uint8_t* binsT, int64_t ldt, const int* ridx, const uint8_t* nid, int64_t n,
@@ -495,7 +498,7 @@ void launch_gbdt_eval_walk(const uint8_t* binsT, int64_t ldt, int64_t n, const i
                            hipStream_t stream);
 void launch_gbdt_predict(const float* X, int64_t n, int ld, int d, const int* feat, const float* thr,
                          const float* leaf, int ntrees, int depth, float base_margin, float* out,
-                         hipStream_t stream);
+                         hipStream_t stream, const uint8_t* dleft = nullptr);  // u8 [ntrees][ni]: NaN goes left
 // Per-row sample weights (float32 [n], finite and >= 0, one per table row): the weighted forms of
 // the gradient-writing kernels.  A row's (g, h) take the factor w in fp64 before the quantisation
 // (reference_gbdt.gradients); w = 1 gives the unweighted word bit for bit, w = 0 the word 0.  The

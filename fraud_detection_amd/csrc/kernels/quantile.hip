@@ -110,16 +110,21 @@ __global__ __launch_bounds__(kQThreads) void qsel_hist_kernel(const float* __res
 }
 
 // One block per feature.  Targets: t = 0 -> rank 0 (the minimum), t >= 1 -> floor(t m / max_bin).
+// counts (int64 [d], null: m for every feature): the feature's rank base m_f <= m in place of m --
+// its non-NaN count, so the quantiles are those of its non-NaN values (NaN sorts last: a rank below
+// m_f never lands on one).  m_f = 0 leaves every target at rank 0, a NaN.
 // Out: per target its top digit, in-bucket rank, and its bucket's run [off, off + cnt) inside the
 // feature's compacted area; cursor[f][b] = run start of a target bucket, -1 for the others.
 __global__ __launch_bounds__(kQThreads) void qsel_plan_kernel(const uint32_t* __restrict__ hist0, int64_t m,
                                                               int max_bin, int* __restrict__ cursor,
                                                               int* __restrict__ tdig, int64_t* __restrict__ trank,
-                                                              int64_t* __restrict__ toff, int64_t* __restrict__ tcnt) {
+                                                              int64_t* __restrict__ toff, int64_t* __restrict__ tcnt,
+                                                              const int64_t* __restrict__ counts) {
   __shared__ uint32_t h[kQBins0];
   __shared__ uint32_t pre[kQBins0];
   __shared__ uint32_t flag[kQBins0];
   const int f = blockIdx.x;
+  if (counts != nullptr) m = min(max(counts[f], (int64_t)0), m);  // a rank stays below the row count
   for (int i = threadIdx.x; i < kQBins0; i += kQThreads) {
     h[i] = hist0[(int64_t)f * kQBins0 + i];
     flag[i] = 0u;
@@ -238,7 +243,7 @@ int64_t quantile_select_ws_bytes(int64_t m, int d) {
 }
 
 void launch_quantile_select(const float* X, int64_t m, int64_t stride, int ld, int d, int max_bin, void* ws,
-                            float* out, hipStream_t stream) {
+                            float* out, hipStream_t stream, const int64_t* counts) {
   if (d < 1 || d > 32 || max_bin < 2 || max_bin > kQThreads || m < 1)
     throw std::runtime_error("quantile_select: need 1 <= d <= 32, 2 <= max_bin <= 256, m >= 1");
   if (m > (int64_t)INT32_MAX) throw std::runtime_error("quantile_select: at most 2^31 - 1 sample rows");
@@ -254,7 +259,7 @@ void launch_quantile_select(const float* X, int64_t m, int64_t stride, int ld, i
     throw std::runtime_error("quantile_select: memset failed");
   const dim3 grid((unsigned)((m + kQChunk - 1) / kQChunk), (unsigned)((d + kQFeatGroup - 1) / kQFeatGroup));
   qsel_hist_kernel<<<grid, kQThreads, 0, stream>>>(X, m, stride, ld, d, hist0);
-  qsel_plan_kernel<<<d, kQThreads, 0, stream>>>(hist0, m, max_bin, cursor, tdig, trank, toff, tcnt);
+  qsel_plan_kernel<<<d, kQThreads, 0, stream>>>(hist0, m, max_bin, cursor, tdig, trank, toff, tcnt, counts);
   qsel_scatter_kernel<<<grid, kQThreads, 0, stream>>>(X, m, stride, ld, d, cursor, runs);
   qsel_final_kernel<<<dim3(max_bin, d), kQThreads, 0, stream>>>(runs, m, max_bin, tdig, trank, toff, tcnt, out);
   check_launch("quantile_select");

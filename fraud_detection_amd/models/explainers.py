@@ -331,6 +331,14 @@ def _check_tree_features(ens, d: int) -> None:
                          f"but the background has {d} columns")
 
 
+def _refuse_default_left(ens, who: str):
+    """The tree explainers' kernels send a NaN right at every node (they compare !(x < thr))."""
+    dl = getattr(ens, "default_left", None)
+    if dl is not None and np.any(dl):
+        raise NotImplementedError(f'{who} does not support ensembles with learned missing-value directions '
+                                  '(GBDTParams.missing_policy="learn" set default_left on some node)')
+
+
 class TreeKernelExplainer:
     """KernelSHAP of a tree ensemble (ops/gbdt.TreeEnsemble trained on standardized rows) over RAW
     inputs: the model is standardize -> ensemble, as served.  Background: <= 128 raw rows of the
@@ -343,6 +351,7 @@ class TreeKernelExplainer:
             raise ValueError("at most 128 background rows (summarize larger sets)")
         if ens.depth > 5:
             raise ValueError("tree KernelSHAP supports depth <= 5 (the reference trains max_depth=5)")
+        _refuse_default_left(ens, "TreeKernelExplainer")
         _check_tree_features(ens, B.shape[1])
         self.ens = ens
         self.d = B.shape[1]
@@ -455,6 +464,7 @@ class TreeExplainer:
             raise ValueError("1..1024 background rows")
         if ens.depth > 5:
             raise ValueError("TreeSHAP kernel supports depth <= 5 (the reference trains max_depth=5)")
+        _refuse_default_left(ens, "TreeExplainer")
         _check_tree_features(ens, B.shape[1])
         self.ens = ens
         self.d = B.shape[1]

@@ -48,13 +48,17 @@ class GBDTClassifier:
                  scale_pos_weight: float = 1.0, base_score: float = 0.5, device: str = "auto",
                  eval_metric=None, early_stopping_rounds: int | None = None, subsample: float = 1.0,
                  colsample_bytree: float = 1.0, colsample_bylevel: float = 1.0, colsample_bynode: float = 1.0,
-                 seed: int | None = None, random_state: int | None = None, **_ignored):
+                 seed: int | None = None, random_state: int | None = None, missing_policy: str = "last_bin",
+                 **_ignored):
         # xgboost-only knobs the reference passes (objective, n_jobs) are accepted and ignored: the
         # objective is binary:logistic.  eval_metric and early_stopping_rounds are constructor
         # arguments as in xgboost >= 1.6; they act only when fit() gets an eval_set (the reference's
         # call passes none: nothing is evaluated).  subsample / colsample_by* switch stochastic
         # boosting on (ops/gbdt.fit_binned); ``random_state`` is the seed when ``seed`` is not given,
         # and without sampling neither has any effect: the fit is deterministic.
+        # missing_policy="learn": rows may hold NaN and every split learns the side they go to
+        # (xgboost's handling of missing values; ops/gbdt.fit_binned); the default "last_bin" bins a
+        # NaN with the feature's largest values.
         if seed is None:
             seed = 0 if random_state is None else random_state
         self.params = gb.GBDTParams(n_estimators=n_estimators, learning_rate=learning_rate, max_depth=max_depth,
@@ -62,7 +66,7 @@ class GBDTClassifier:
                                     max_bin=max_bin, scale_pos_weight=scale_pos_weight, base_score=base_score,
                                     subsample=subsample, colsample_bytree=colsample_bytree,
                                     colsample_bylevel=colsample_bylevel, colsample_bynode=colsample_bynode,
-                                    seed=int(seed))
+                                    seed=int(seed), missing_policy=missing_policy)
         self.device = device
         self.eval_metric = eval_metric
         self.early_stopping_rounds = early_stopping_rounds
@@ -301,6 +305,9 @@ class GBDTPipeline:
                  checkpoint_every: int = 10):
         self.cfg = cfg or TrainConfig()
         self.params = params or gb.GBDTParams()
+        if self.params.learn_missing:
+            raise NotImplementedError('GBDTPipeline does not support missing_policy="learn": the scaler, k-NN and '
+                                      "SMOTE of the recipe have no NaN semantics; use GBDTClassifier")
         self.comm = comm
         self.spw = scale_pos_weight
         self.checkpoint_dir, self.checkpoint_every = checkpoint_dir, checkpoint_every

@@ -86,6 +86,9 @@ class DeviceGBDTCV:
         self.early_stopping_rounds = early_stopping_rounds
         self.cfg = cfg or TrainConfig()
         self.params = params or gb.GBDTParams()
+        if self.params.learn_missing:
+            raise NotImplementedError('DeviceGBDTCV does not support missing_policy="learn": the scaler, k-NN and '
+                                      "SMOTE of the fold recipe have no NaN semantics; use GBDTClassifier")
         self.n_folds = int(n_folds)
         self.seed = int(seed)
         self.spw = scale_pos_weight

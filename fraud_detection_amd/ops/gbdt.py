@@ -47,9 +47,16 @@ class GBDTParams:
     colsample_bylevel: float = 1.0
     colsample_bynode: float = 1.0
     seed: int = 0
+    # "last_bin": a NaN is binned with the feature's largest values and always goes right.
+    # "learn": NaN gets a bin slot of its own and every split learns which side it goes to
+    # (xgboost's sparsity-aware split finding; reference_gbdt's module docstring has the rules).
+    missing_policy: str = "last_bin"
 
+    MISSING_POLICIES = ("last_bin", "learn")
+    # fields a checkpoint signature names only off their defaults (older checkpoints resume): the
+    # sampling fields and, added the same way, the missing policy
     SAMPLING_DEFAULTS = {"subsample": 1.0, "colsample_bytree": 1.0, "colsample_bylevel": 1.0,
-                         "colsample_bynode": 1.0, "seed": 0}
+                         "colsample_bynode": 1.0, "seed": 0, "missing_policy": "last_bin"}
 
     @property
     def colsampled(self) -> bool:
@@ -59,7 +66,13 @@ class GBDTParams:
     def sampled(self) -> bool:
         return self.subsample != 1.0 or self.colsampled
 
+    @property
+    def learn_missing(self) -> bool:
+        return self.missing_policy == "learn"
+
     def validate(self):
+        if self.missing_policy not in self.MISSING_POLICIES:
+            raise ValueError(f"missing_policy must be one of {self.MISSING_POLICIES}, got {self.missing_policy!r}")
         for name in ("subsample", "colsample_bytree", "colsample_bylevel", "colsample_bynode"):
             v = float(getattr(self, name))
             if not 0.0 < v <= 1.0:  # NaN fails too
@@ -95,6 +108,11 @@ class TreeEnsemble:
     nbins: np.ndarray  # [d] int32
     base_score: float = 0.5
     params: dict = field(default_factory=dict)
+    default_left: np.ndarray | None = None  # [T, 2^D - 1] uint8: a NaN goes left at the node; None: all zero
+
+    @property
+    def has_default_left(self) -> bool:
+        return self.default_left is not None and bool(np.any(self.default_left))
 
     @property
     def n_trees(self) -> int:
@@ -121,18 +139,21 @@ class TreeEnsemble:
         return np.where(cnt > 0, tot / np.maximum(cnt, 1), 0.0)
 
     def to_dict(self) -> dict:
-        return {"format": "fdx-gbdt/1", "depth": self.depth, "base_score": self.base_score,
-                "params": self.params, "feat": self.feat.tolist(), "bin": self.bin.tolist(),
-                "thr": [[float(v) if np.isfinite(v) else "inf" for v in row] for row in self.thr],
-                "gain": self.gain.tolist(), "leaf": self.leaf.tolist(),
-                "cuts": [[float(v) if np.isfinite(v) else "inf" for v in row[:nb]] for row, nb in zip(self.cuts, self.nbins)],
-                "nbins": self.nbins.tolist()}
+        o = {"format": "fdx-gbdt/1", "depth": self.depth, "base_score": self.base_score,
+             "params": self.params, "feat": self.feat.tolist(), "bin": self.bin.tolist(),
+             "thr": [[float(v) if np.isfinite(v) else ("-inf" if v == -np.inf else "inf") for v in row] for row in self.thr],
+             "gain": self.gain.tolist(), "leaf": self.leaf.tolist(),
+             "cuts": [[float(v) if np.isfinite(v) else "inf" for v in row[:nb]] for row, nb in zip(self.cuts, self.nbins)],
+             "nbins": self.nbins.tolist()}
+        if self.has_default_left:  # an ensemble without a default-left node serialises as it always did
+            o["default_left"] = np.asarray(self.default_left, np.uint8).tolist()
+        return o
 
     @classmethod
     def from_dict(cls, o: dict) -> "TreeEnsemble":
         if o.get("format") != "fdx-gbdt/1":
             raise ValueError("not an fdx-gbdt/1 model")
-        f = lambda v: np.inf if v == "inf" else float(v)  # noqa: E731
+        f = lambda v: np.inf if v == "inf" else (-np.inf if v == "-inf" else float(v))  # noqa: E731
         depth = int(o["depth"])
         ni = (1 << depth) - 1
         nbins = np.asarray(o["nbins"], np.int32)
@@ -144,13 +165,38 @@ class TreeEnsemble:
                    thr=np.asarray([[f(v) for v in row] for row in o["thr"]], np.float32).reshape(-1, ni),
                    gain=np.asarray(o["gain"], np.float64).reshape(-1, ni),
                    leaf=np.asarray(o["leaf"], np.float32).reshape(-1, 1 << depth), cuts=cuts, nbins=nbins,
-                   base_score=float(o["base_score"]), params=dict(o.get("params", {})))
+                   base_score=float(o["base_score"]), params=dict(o.get("params", {})),
+                   default_left=(np.asarray(o["default_left"], np.uint8).reshape(-1, ni)
+                                 if o.get("default_left") is not None else None))
+
+
+# Device-side split words (csrc/kernels/gbdt.hip goes_right): a default-left split of bin b (b = -1:
+# the missing rows alone go left) is 0x200 | (b + 1), a word in [0x200, 0x3ff]; every other word is
+# the split bin itself, missing rows going right -- what the `bin` arrays always held.  With
+# s = (w in [0x200, 0x3ff]) the walk on a bin byte v is right = ((v + s) & 0xff) > w - (s << 9):
+# v > w for the old words; for the new ones byte 255 wraps to 0 and goes left, every other byte
+# compares v + 1 > b + 1.
+def encode_bin_words(binv: np.ndarray, default_left: np.ndarray | None) -> np.ndarray:
+    binv = np.asarray(binv, np.int32)
+    if default_left is None:
+        return binv
+    return np.where(np.asarray(default_left) != 0, 0x200 | (binv + 1), binv).astype(np.int32)
+
+
+def decode_bin_words(words: np.ndarray):
+    """(bin int32, default_left uint8) of device split words."""
+    words = np.asarray(words, np.int32)
+    dl = (words >> 9) == 1
+    return np.where(dl, (words & 0x1FF) - 1, words).astype(np.int32), dl.astype(np.uint8)
 
 
 # ---- binning ---------------------------------------------------------------------------------
-def quantile_cuts(X: torch.Tensor, max_bin: int = MAX_BIN, sample_rows: int = 1 << 20, comm=None):
+def quantile_cuts(X: torch.Tensor, max_bin: int = MAX_BIN, sample_rows: int = 1 << 20, comm=None,
+                  missing: bool = False):
     """Per-feature quantile cuts from a deterministic strided row sample.  Under DP every rank
-    contributes a sample and the cuts come from the gathered sample, so all ranks agree."""
+    contributes a sample and the cuts come from the gathered sample, so all ranks agree.
+    ``missing``: the quantiles of a feature are taken over the sample's non-NaN values only
+    (reference_gbdt.quantile_cuts); at most 255 real bins, byte 255 being the missing slot."""
     n, d = X.shape
     if d > MAX_FEAT:
         raise ValueError(f"at most {MAX_FEAT} features")
@@ -163,7 +209,7 @@ def quantile_cuts(X: torch.Tensor, max_bin: int = MAX_BIN, sample_rows: int = 1 
     else:
         src, m, step = X, min(per, (n + stride - 1) // stride), stride
     if not src.is_cuda:
-        return R.quantile_cuts(src[::step][:m].float().numpy(), max_bin)
+        return R.quantile_cuts(src[::step][:m].float().numpy(), max_bin, missing)
     # Exact order statistics by a native radix select (quantile.hip): the minimum and the max_bin - 1
     # quantile rows of the sample come back to the host, where deduplication is trivial.  Selection
     # is exact, so the cuts equal the CPU oracle's (np.sort) on the same sample.
@@ -171,21 +217,31 @@ def quantile_cuts(X: torch.Tensor, max_bin: int = MAX_BIN, sample_rows: int = 1 
         src, step = src[::step][:m].float().contiguous(), 1
     nat = native()
     ws = torch.empty(nat.quantile_select_ws_bytes(m, d), dtype=torch.uint8, device=src.device)
+    if missing:
+        # the same select with per-feature rank bases m_f = the feature's non-NaN count, which stays
+        # on the device; NaN sorts last, so a rank below m_f never lands on one, and a feature
+        # without a value returns NaN as its minimum (cuts_from_sorted_picks: one bin)
+        max_bin = min(max_bin, MAX_BIN - 1)
+        samp = src[::step][:m]
+        counts = (samp == samp).sum(0, dtype=torch.int64).contiguous()
     picks = torch.empty((max_bin, d), dtype=torch.float32, device=src.device)
-    nat.quantile_select(ptr(src), m, step, src.stride(0), d, max_bin, ptr(ws), ptr(picks), stream_of(src))
+    nat.quantile_select(ptr(src), m, step, src.stride(0), d, max_bin, ptr(ws), ptr(picks), stream_of(src),
+                        *((ptr(counts),) if missing else ()))
     picks = picks.cpu().numpy()
-    return R.cuts_from_sorted_picks(picks[1:], picks[0], max_bin)
+    return R.cuts_from_sorted_picks(picks[1:], picks[0], max_bin, missing)
 
 
-def bin_rows(X: torch.Tensor, cuts: np.ndarray, nbins: np.ndarray, out: torch.Tensor | None = None) -> torch.Tensor:
+def bin_rows(X: torch.Tensor, cuts: np.ndarray, nbins: np.ndarray, out: torch.Tensor | None = None,
+             missing: bool = False) -> torch.Tensor:
     """u8 [n, 32] bins (features in bytes 0..d-1).  ``out``: a [n, 32] u8 view to write (e.g. the
-    SMOTE tail of a binned table)."""
+    SMOTE tail of a binned table).  ``missing``: a NaN goes to byte 255, the missing slot (the cuts
+    then have at most 255 real bins), instead of the feature's last bin."""
     n, d = X.shape
     if out is not None and (tuple(out.shape) != (n, R.ROW_BYTES) or out.dtype != torch.uint8
                             or not out.is_contiguous() or out.device != X.device):
         raise ValueError("out must be a contiguous u8 [n, 32] tensor on X's device")
     if not X.is_cuda:
-        b = torch.from_numpy(R.bin_rows(X.numpy(), cuts, nbins))
+        b = torch.from_numpy(R.bin_rows(X.numpy(), cuts, nbins, missing))
         return out.copy_(b) if out is not None else b
     if X.dtype != torch.float32 or X.stride(1) != 1:
         raise ValueError("X must be float32 with unit column stride")
@@ -193,8 +249,10 @@ def bin_rows(X: torch.Tensor, cuts: np.ndarray, nbins: np.ndarray, out: torch.Te
     out = out if out is not None else torch.empty((n, R.ROW_BYTES), dtype=torch.uint8, device=X.device)
     ct = torch.from_numpy(np.ascontiguousarray(cuts[:d])).to(X.device)
     nt = torch.from_numpy(np.ascontiguousarray(nbins[:d])).to(X.device)
+    if missing and int(np.max(nbins[:d], initial=0)) > MAX_BIN - 1:
+        raise ValueError("missing: byte 255 is the missing slot, at most 255 real bins per feature")
     if n:
-        m.gbdt_bin(ptr(X), n, X.stride(0), d, ptr(ct), ptr(nt), ptr(out), stream_of(X))
+        m.gbdt_bin(ptr(X), n, X.stride(0), d, ptr(ct), ptr(nt), ptr(out), stream_of(X), *((True,) if missing else ()))
     return out
 
 
@@ -457,8 +515,8 @@ def fit(X: torch.Tensor, y: torch.Tensor, params: GBDTParams | None = None, comm
     if d > MAX_FEAT:
         raise ValueError(f"at most {MAX_FEAT} features")
     if cuts is None:
-        cuts = quantile_cuts(X, p.max_bin, p.cut_sample_rows, comm)
-    bins = bin_rows(X, cuts[0], cuts[1])
+        cuts = quantile_cuts(X, p.max_bin, p.cut_sample_rows, comm, p.learn_missing)
+    bins = bin_rows(X, cuts[0], cuts[1], missing=p.learn_missing)
     return fit_binned(bins, y, cuts, p, comm=comm, sample_weight_pos=sample_weight_pos, return_margin=return_margin,
                       checkpoint=checkpoint, checkpoint_every=checkpoint_every, use_graph=use_graph,
                       eval_set=eval_set, eval_metric=eval_metric, early_stopping_rounds=early_stopping_rounds,
@@ -533,6 +591,18 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
     (gbdt_hist_l0_fused has no weighted variant).  ``checkpoint=`` with ``sample_weight`` raises
     NotImplementedError: the signature would have to cover the weights.
 
+    Missing values (``missing_policy="learn"`` of GBDTParams): byte 255 of a binned row is the missing
+    slot (bin_rows(..., missing=True); the cuts hold at most 255 real bins), the split scan learns for
+    every split which side the slot's rows take, and the ensemble carries the choice in
+    ``default_left`` (reference_gbdt's module docstring has the rules; the device matches it
+    bitwise).  Histograms, leaves, gradients, sampling, weights and evaluation are what they were.
+    On the device the direction travels inside the round's ``bin`` words (encode_bin_words), so
+    partition, margin and eval walks need no further argument; the host decodes them when it copies
+    the trees back and encodes them again on a checkpoint resume.  Float eval rows are binned with
+    the same rule.  Under "learn" FDX_GBDT_FUSE_MARGIN=1 falls back to the eager, unfused round, as
+    under sampling and weights: the fused level-0 pass (gbdt_hist_l0_fused) has its own walk, which
+    knows no directions.  The hipGraph path replays the same kernels and needs nothing.
+
     Evaluation weights (``eval_sample_weight``, xgboost's sample_weight_eval_set): float32 [m] for an
     ``(Xv, yv)`` set, [hole_len] for ``eval_set="hole"``, finite and >= 0 with a positive entry.
     "logloss" and "error" become weighted means and stay exact integers
@@ -571,6 +641,10 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
     base_margin = float(np.log(p.base_score / (1.0 - p.base_score)))
     dist = comm is not None and comm.world_size > 1
     sub_on, seed = p.subsample != 1.0, int(p.seed)
+    learn = p.learn_missing
+    if learn and int(np.max(nbins, initial=0)) > MAX_BIN - 1:
+        raise ValueError('missing_policy="learn": byte 255 is the missing slot, the cuts may hold at most 255 '
+                         "real bins per feature (quantile_cuts(..., missing=True))")
     thresh = R.sample_threshold(p.subsample) if sub_on else 0
     if row_offset is None:
         row_offset = 0
@@ -582,7 +656,9 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
     # allowed-feature bits of every (round, heap node), drawn on the host once per fit
     fmasks = R.feature_mask_table(seed, T, d, D, p.colsample_bytree, p.colsample_bylevel,
                                   p.colsample_bynode) if p.colsampled else None
-    ens_kw = dict(depth=D, cuts=cuts_np, nbins=nbins, base_score=p.base_score, params={**p.__dict__, "seed": seed})
+    # the policy is named only where it is not the default: a "last_bin" model serialises as before
+    ens_kw = dict(depth=D, cuts=cuts_np, nbins=nbins, base_score=p.base_score,
+                  params={**{k: v for k, v in p.__dict__.items() if k != "missing_policy" or learn}, "seed": seed})
     req = _eval_request(eval_set, eval_metric, early_stopping_rounds, hl, checkpoint,
                         comm is not None and comm.world_size > 1, T)
     ev = None
@@ -598,7 +674,7 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
             else:
                 if Xv.dim() != 2 or Xv.shape[1] != d:
                     raise ValueError(f"eval_set: the fit has {d} features, Xv has {tuple(Xv.shape)}")
-                bins_v = bin_rows(Xv if Xv.is_cuda else Xv.float(), cuts_np, nbins)
+                bins_v = bin_rows(Xv if Xv.is_cuda else Xv.float(), cuts_np, nbins, missing=learn)
             yv = yv.contiguous()
     w_ev = None
     if eval_sample_weight is not None:
@@ -635,10 +711,11 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
                                cuts=cuts_np, nbins=nbins, n=n_all, d=d, **({"hole": [ha, hl]} if hl else {}), **offs)
     prev, t0 = _resume(checkpoint, sig, T)
 
-    def _save(t_done, feat, binv, thr, gain, leaf):
+    def _save(t_done, feat, binv, thr, gain, leaf, dleft=None):
         if checkpoint is not None and t_done > 0:
+            extra = {} if dleft is None else {"default_left": dleft[:t_done]}
             checkpoint.save(t_done, {"feat": feat[:t_done], "bin": binv[:t_done], "thr": thr[:t_done],
-                                     "gain": gain[:t_done], "leaf": leaf[:t_done]},
+                                     "gain": gain[:t_done], "leaf": leaf[:t_done], **extra},
                             {"signature": sig, "trees_done": t_done, "kind": "gbdt"})
             fault = os.environ.get("FDX_FAULT", "")
             if fault.startswith("gbdt_crash_after_trees=") and t_done >= int(fault.split("=", 1)[1]):
@@ -647,6 +724,7 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
     if not bins.is_cuda:
         feat = np.zeros((T, ni), np.int32); binv = np.zeros((T, ni), np.int32)
         thr = np.zeros((T, ni), np.float32); gain = np.zeros((T, ni)); leaf = np.zeros((T, nl), np.float32)
+        dleft = np.zeros((T, ni), np.uint8) if learn else None
         b_all = bins.numpy()
         y_all = y.numpy()
         keep = np.r_[0:ha, ha + hl:n]
@@ -655,7 +733,10 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
         margin = np.full(n_fit, np.float32(base_margin), np.float32)
         if t0:
             feat[:t0], binv[:t0], thr[:t0], gain[:t0], leaf[:t0] = (prev[k] for k in ("feat", "bin", "thr", "gain", "leaf"))
-            margin = R.predict_margin_bins(b, feat[:t0], binv[:t0], leaf[:t0], D, base_margin)
+            if learn:
+                dleft[:t0] = prev["default_left"]
+            margin = R.predict_margin_bins(b, feat[:t0], binv[:t0], leaf[:t0], D, base_margin,
+                                           None if dleft is None else dleft[:t0])
         if ev is not None:  # the eval rows' bins, labels and running margin (the device's eval walk)
             b_ev, y_ev = (b_all[ha:ha + hl], y_all[ha:ha + hl]) if ev_kind == "hole" else (bins_v.numpy(), yv.numpy())
             m_ev = np.full(b_ev.shape[0], np.float32(base_margin), np.float32)
@@ -664,13 +745,17 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
             if sub_on:  # global ids of the fit's rows: a row keeps its table index around the hole
                 q[~R.row_sample_mask(seed, t, keep + row_offset, p.subsample)] = 0
             tr, node = R.build_tree(b, q, cuts_np, nbins, D, p.reg_lambda, p.min_child_weight, p.gamma,
-                                    p.learning_rate, gscale, hscale, comm, None if fmasks is None else fmasks[t])
+                                    p.learning_rate, gscale, hscale, comm, None if fmasks is None else fmasks[t],
+                                    learn)
             feat[t], binv[t], thr[t], gain[t], leaf[t] = tr.feat, tr.bin, tr.thr, tr.gain, tr.leaf
+            if learn:
+                dleft[t] = tr.default_left
             margin = (margin + tr.leaf[node]).astype(np.float32)
             if (t + 1) % max(1, checkpoint_every) == 0 or t + 1 == T:
-                _save(t + 1, feat, binv, thr, gain, leaf)
+                _save(t + 1, feat, binv, thr, gain, leaf, dleft)
             if ev is not None:
-                m_ev = (m_ev + R.predict_margin_bins(b_ev, feat[t:t + 1], binv[t:t + 1], leaf[t:t + 1], D, 0.0)
+                m_ev = (m_ev + R.predict_margin_bins(b_ev, feat[t:t + 1], binv[t:t + 1], leaf[t:t + 1], D, 0.0,
+                                                     None if dleft is None else dleft[t:t + 1])
                         ).astype(np.float32)
                 rec = R.eval_record(m_ev, y_ev) if w_ev is None else \
                     R.eval_record_weighted(m_ev, y_ev, w_ev.numpy(), ev_wscale)
@@ -682,15 +767,16 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
         if ev is not None and ev.n_keep < T:  # early stop: keep [: best + 1], margins of the kept trees
             k = ev.n_keep
             feat, binv, thr, gain, leaf = feat[:k], binv[:k], thr[:k], gain[:k], leaf[:k]
-            margin = R.predict_margin_bins(b, feat, binv, leaf, D, base_margin)
-        ens = TreeEnsemble(feat=feat, bin=binv, thr=thr, gain=gain, leaf=leaf, **ens_kw)
+            dleft = None if dleft is None else dleft[:k]
+            margin = R.predict_margin_bins(b, feat, binv, leaf, D, base_margin, dleft)
+        ens = TreeEnsemble(feat=feat, bin=binv, thr=thr, gain=gain, leaf=leaf, default_left=dleft, **ens_kw)
         tail = () if ev is None else (ev.result(),)
         if not return_margin:
             return (ens, *tail) if tail else ens
         full = np.empty(n, np.float32)
         full[keep] = margin
         if hl:
-            full[ha:ha + hl] = R.predict_margin_bins(b_all[ha:ha + hl], feat, binv, leaf, D, base_margin)
+            full[ha:ha + hl] = R.predict_margin_bins(b_all[ha:ha + hl], feat, binv, leaf, D, base_margin, dleft)
         return (ens, torch.from_numpy(full), *tail)
 
     m = native()
@@ -712,6 +798,8 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
     leaf = torch.empty((T, nl), dtype=torch.float32, device=dev)
     margin = torch.full((n,), base_margin, dtype=torch.float32, device=dev)
     if t0:
+        if learn:  # the device's bin words carry the direction
+            prev = {**prev, "bin": encode_bin_words(prev["bin"], prev["default_left"])}
         for name, dst in (("feat", feat), ("bin", binv), ("thr", thr), ("gain", gain), ("leaf", leaf)):
             dst[:t0].copy_(torch.from_numpy(np.ascontiguousarray(prev[name])))
         for t in range(t0):  # the margins of the saved trees, by the round's own margin kernel
@@ -747,6 +835,7 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
                           ptr(ws.node_r), ws.node_r.numel())
         cur = 0
         fmask_arg = () if fm_dev is None else (ptr(fm_dev[t]),)  # the round's [ni] mask row; none: every feature
+        miss_arg = {"missing": True} if learn else {}  # the scan learns the missing slot's side; o_bin gets words
         for level in range(D):
             h0, nn = (1 << level) - 1, 1 << level
             if level == 0 and prev is not None:
@@ -759,7 +848,8 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
             if dist:
                 comm.all_reduce_(ws.hist[h0 * HIST_ENTRIES:(h0 + nn) * HIST_ENTRIES])
             m.gbdt_split(ptr(ws.hist), ptr(ws.gcnt), level, d, ptr(nt), ptr(ct), ginv, hinv, lam, mcw, gam,
-                         ptr(o_feat), ptr(o_bin), ptr(o_thr), ptr(o_gain), ptr(ws.ng), ptr(ws.nh), st, *fmask_arg)
+                         ptr(o_feat), ptr(o_bin), ptr(o_thr), ptr(o_gain), ptr(ws.ng), ptr(ws.nh), st, *fmask_arg,
+                         **miss_arg)
             if level == D - 1:
                 break  # leaves: the margin walk and gbdt_leaf (split-kernel child sums) need no partition
             if n_fit:
@@ -791,6 +881,11 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
 
     def after_round(t):
         if checkpoint is not None and ((t + 1) % max(1, checkpoint_every) == 0 or t + 1 == T):
+            if learn:  # checkpoints hold bin / default_left, not the device's words
+                dl = (binv[:t + 1] >> 9) == 1
+                _save(t + 1, feat, torch.where(dl, (binv[:t + 1] & 0x1FF) - 1, binv[:t + 1]), thr, gain, leaf,
+                      dl.to(torch.uint8))
+                return
             _save(t + 1, feat, binv, thr, gain, leaf)  # device -> host copy: syncs every k rounds only
 
     # hipGraph: a round is ~5 + 6*D launches with static shapes, so after one eager round it is
@@ -807,9 +902,10 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
     # Sampling keeps them too, unfused: a recorded round and the fused level-0 pass bake the round's
     # constants in, and the round number (row sample, mask row) is one of them.
     # Per-row weights keep them as well: the fused level-0 pass has no weighted variant.
+    # missing_policy="learn" drops the fused pass only (its walk knows no directions).
     graphable = use_graph and not dist and n > 0 and T - t0 >= 3 and ev is None and not p.sampled and wt is None
     fuse_margin = (os.environ.get("FDX_GBDT_FUSE_MARGIN", "0") == "1" and not graphable and ev is None
-                   and not p.sampled and wt is None)
+                   and not p.sampled and wt is None and not learn)
     graph = None
     if ev is not None:
         from . import metrics as metric_ops
@@ -899,9 +995,13 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
         after_round(t)
         if ev is not None:
             eval_round(t)
+    def host_bins(words):  # (bin, default_left) of the device's split words
+        return decode_bin_words(words.cpu().numpy()) if learn else (words.cpu().numpy(), None)
+
     if ev is None:
-        ens = TreeEnsemble(feat=feat.cpu().numpy(), bin=binv.cpu().numpy(), thr=thr.cpu().numpy(),
-                           gain=gain.cpu().numpy(), leaf=leaf.cpu().numpy(), **ens_kw)
+        bin_np, dl_np = host_bins(binv)
+        ens = TreeEnsemble(feat=feat.cpu().numpy(), bin=bin_np, thr=thr.cpu().numpy(),
+                           gain=gain.cpu().numpy(), leaf=leaf.cpu().numpy(), default_left=dl_np, **ens_kw)
         return (ens, margin) if return_margin else ens
     # the records still in flight, in round order (the rule may fire on one of them: the rounds
     # enqueued past it are dropped, exactly as if the host had seen the record in time)
@@ -914,8 +1014,9 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
         for t in range(k):
             m.gbdt_margin(ptr(binsT), ldt, n, ptr(feat[t]), ptr(binv[t]), ptr(leaf[t]), D, ptr(margin), ptr(y), spw,
                           gscale, hscale, 0, st0)
-    ens = TreeEnsemble(feat=feat[:k].cpu().numpy(), bin=binv[:k].cpu().numpy(), thr=thr[:k].cpu().numpy(),
-                       gain=gain[:k].cpu().numpy(), leaf=leaf[:k].cpu().numpy(), **ens_kw)
+    bin_np, dl_np = host_bins(binv[:k])
+    ens = TreeEnsemble(feat=feat[:k].cpu().numpy(), bin=bin_np, thr=thr[:k].cpu().numpy(),
+                       gain=gain[:k].cpu().numpy(), leaf=leaf[:k].cpu().numpy(), default_left=dl_np, **ens_kw)
     return (ens, margin, ev.result()) if return_margin else (ens, ev.result())
 
 
@@ -929,6 +1030,9 @@ class DeviceEnsemble:
         self.feat = torch.from_numpy(np.ascontiguousarray(ens.feat)).to(device)
         self.thr = torch.from_numpy(np.ascontiguousarray(ens.thr)).to(device)
         self.leaf = torch.from_numpy(np.ascontiguousarray(ens.leaf)).to(device)
+        # None: no node sends a NaN left (gbdt_predict's null pointer, the walk it always did)
+        self.dleft = torch.from_numpy(np.ascontiguousarray(ens.default_left, np.uint8)).to(device) \
+            if ens.has_default_left else None
 
 
 def predict_margin(X: torch.Tensor, ens: TreeEnsemble, dens: DeviceEnsemble | None = None,
@@ -943,14 +1047,16 @@ def predict_margin(X: torch.Tensor, ens: TreeEnsemble, dens: DeviceEnsemble | No
         raise ValueError(f"n_trees must be in [0, {ens.n_trees}]")
     if not X.is_cuda:
         return torch.from_numpy(R.predict_margin(X.numpy(), ens.feat[:k], ens.thr[:k], ens.leaf[:k], ens.depth,
-                                                 ens.base_margin))
+                                                 ens.base_margin,
+                                                 ens.default_left[:k] if ens.has_default_left else None))
     if X.dtype != torch.float32 or X.stride(1) != 1:
         raise ValueError("X must be float32 with unit column stride")
     dens = dens if dens is not None and dens.device == X.device else DeviceEnsemble(ens, X.device)
     out = torch.empty(n, dtype=torch.float32, device=X.device)
     if n:
         native().gbdt_predict(ptr(X), n, X.stride(0), d, ptr(dens.feat), ptr(dens.thr), ptr(dens.leaf), k,
-                              ens.depth, ens.base_margin, ptr(out), stream_of(X))
+                              ens.depth, ens.base_margin, ptr(out), stream_of(X),
+                              *((ptr(dens.dleft),) if getattr(dens, "dleft", None) is not None else ()))
     return out
 
 

@@ -18,6 +18,23 @@ same tie rules, so a device fit given the same quantised gradients builds bit-id
   min_child_weight = 0 (an empty child contributes 0^2/l = 0 either way, but a child with H = 0,
   G != 0 contributes G^2/l here), so it is deliberately not adopted.
 
+Missing values (``missing=True``, GBDTParams.missing_policy = "learn"; default off, and off means
+every function here is what it was):
+
+* cuts: per feature over the sample's non-NaN values only, ranks floor(t m_f / B) with m_f the
+  feature's non-NaN count and B = min(max_bin, 255); m_f = 0 gives nbins = 1, every cut +inf;
+  nbins <= 255 counts real bins only;
+* binning: a NaN of either sign goes to byte 255 (MISSING_BIN) for every feature, every other value
+  (+-inf included) as before;
+* split scan: with (Gm, Hm) the sums of slot 255, a feature's candidates in tie order are b = -1
+  with default left (left = the missing rows only; stored bin -1, thr -inf, default_left 1), then
+  for b = 0 .. nbins - 2 "missing right" (GL = prefix(b), default_left 0) and "missing left"
+  (GL = prefix(b) + Gm, default_left 1).  Same gain formula and validity tests; ties go to the
+  lowest feature, then the lowest b, then default_left 0 -- so NaN-free data gives default_left 0;
+* direction: fp32 rows go right iff isnan(x) ? !default_left : !(x < thr); binned rows iff
+  (v == 255) ? !default_left : v > bin.  x < -inf is false for every non-NaN x, so the b = -1
+  split sends exactly the missing rows left in both walks.
+
 xgboost itself is not installed in this image, so parity with xgboost is "unpinned"; the
 semantics above follow xgboost's hist updater (train_model.py:69-80 uses XGBClassifier).
 """
@@ -29,16 +46,25 @@ import numpy as np
 
 MAX_BIN = 256
 ROW_BYTES = 32
+MISSING_BIN = 255  # the byte of a NaN under missing=True (real bins are then 0 .. 254)
 
 
-def quantile_cuts(sample: np.ndarray, max_bin: int = MAX_BIN):
-    """sample: [m, d] float32.  Returns (cuts [d, 256] float32 padded with +inf, nbins [d] int32)."""
+def quantile_cuts(sample: np.ndarray, max_bin: int = MAX_BIN, missing: bool = False):
+    """sample: [m, d] float32.  Returns (cuts [d, 256] float32 padded with +inf, nbins [d] int32).
+    ``missing``: the quantiles of every feature over its non-NaN values only (module docstring)."""
     sample = np.asarray(sample, dtype=np.float32)
     m, d = sample.shape
     if max_bin < 2 or max_bin > MAX_BIN:
         raise ValueError("max_bin must be in [2, 256]")
     cuts = np.full((d, MAX_BIN), np.inf, dtype=np.float32)
     nbins = np.zeros(d, dtype=np.int32)
+    if missing:
+        B = min(max_bin, MAX_BIN - 1)
+        srt = np.sort(sample, axis=0)  # NaN last, whatever its sign
+        mf = (sample == sample).sum(0).astype(np.int64)
+        idx = (np.arange(1, B, dtype=np.int64)[:, None] * mf[None, :]) // B  # < mf wherever mf > 0
+        picks = np.take_along_axis(srt, idx, 0) if m else np.full((B - 1, d), np.nan, np.float32)
+        return cuts_from_sorted_picks(picks, srt[0] if m else np.full(d, np.nan, np.float32), B, True)
     if m == 0:
         nbins[:] = 1
         return cuts, nbins
@@ -47,13 +73,20 @@ def quantile_cuts(sample: np.ndarray, max_bin: int = MAX_BIN):
     return cuts_from_sorted_picks(srt[idx], srt[0], max_bin)
 
 
-def cuts_from_sorted_picks(picks: np.ndarray, vmin: np.ndarray, max_bin: int = MAX_BIN):
-    """picks [max_bin-1, d]: sample values at the quantile positions; vmin [d]: sample minimum."""
+def cuts_from_sorted_picks(picks: np.ndarray, vmin: np.ndarray, max_bin: int = MAX_BIN, missing: bool = False):
+    """picks [max_bin-1, d]: sample values at the quantile positions; vmin [d]: sample minimum.
+    ``missing``: picks and minimum were taken over the non-NaN values (max_bin <= 255); a NaN
+    minimum means the feature has none (NaN sorts last): nbins = 1, every cut +inf."""
     picks = np.asarray(picks, dtype=np.float32)
     d = picks.shape[1]
     cuts = np.full((d, MAX_BIN), np.inf, dtype=np.float32)
     nbins = np.zeros(d, dtype=np.int32)
+    if missing and max_bin > MAX_BIN - 1:
+        raise ValueError("missing: at most 255 real bins")
     for f in range(d):
+        if missing and vmin[f] != vmin[f]:
+            nbins[f] = 1
+            continue
         c = np.unique(picks[:, f])
         c = c[c > vmin[f]][: max_bin - 1]
         cuts[f, : len(c)] = c
@@ -61,13 +94,16 @@ def cuts_from_sorted_picks(picks: np.ndarray, vmin: np.ndarray, max_bin: int = M
     return cuts, nbins
 
 
-def bin_rows(X: np.ndarray, cuts: np.ndarray, nbins: np.ndarray) -> np.ndarray:
+def bin_rows(X: np.ndarray, cuts: np.ndarray, nbins: np.ndarray, missing: bool = False) -> np.ndarray:
+    """``missing``: a NaN goes to byte MISSING_BIN instead of the feature's last bin."""
     X = np.asarray(X, dtype=np.float32)
     n, d = X.shape
     out = np.zeros((n, ROW_BYTES), dtype=np.uint8)
     for f in range(d):
         nb = int(nbins[f])
         out[:, f] = np.searchsorted(cuts[f, :nb], X[:, f], side="right").clip(0, nb - 1)
+        if missing:
+            out[np.isnan(X[:, f]), f] = MISSING_BIN
     return out
 
 
@@ -144,13 +180,18 @@ class TreeArrays:
     thr: np.ndarray    # [ni] float32 (+inf when not split)
     gain: np.ndarray   # [ni] float64
     leaf: np.ndarray   # [nl] float32
+    default_left: np.ndarray | None = None  # [ni] uint8 (build_tree with missing=True), else None
 
 
 def best_split(H: np.ndarray, nbins: np.ndarray, ginv: float, hinv: float, lam: float, mcw: float,
-               fmask: int | None = None):
+               fmask: int | None = None, missing: bool = False):
     """H: int64 [d, 256, 2] of one node.  Returns (gain, feature, bin, GLq, HLq, Gq, Hq).
     ``fmask``: bit f set = feature f may be picked (None: all).  The node totals come from feature
-    0's sums whether or not feature 0 is allowed; with no valid allowed split the gain is -inf."""
+    0's sums whether or not feature 0 is allowed; with no valid allowed split the gain is -inf.
+    ``missing``: slot 255 holds the missing rows' sums and the scan learns their side (module
+    docstring); the return value gains default_left as its eighth element and bin may be -1."""
+    if missing:
+        return _best_split_missing(H, nbins, ginv, hinv, lam, mcw, fmask)
     d = H.shape[0]
     cg = np.cumsum(H[:, :, 0], axis=1)
     chs = np.cumsum(H[:, :, 1], axis=1)
@@ -174,10 +215,53 @@ def best_split(H: np.ndarray, nbins: np.ndarray, ginv: float, hinv: float, lam: 
     return float(gain[f, bb]), f, bb, int(cg[f, bb]), int(chs[f, bb]), Gq, Hq
 
 
+def _best_split_missing(H, nbins, ginv, hinv, lam, mcw, fmask):
+    """best_split with a learned side for slot 255.  Candidate (b, dl) sits at column 2 (b + 1) + dl
+    of a [d, 512] gain table -- the tie order -- so one argmax picks the lowest feature, then the
+    lowest b (-1 first), then default_left 0.  Column 0 (b = -1, nothing left) is no candidate."""
+    d = H.shape[0]
+    cg = np.cumsum(H[:, :, 0], axis=1)
+    chs = np.cumsum(H[:, :, 1], axis=1)
+    Gq, Hq = int(cg[0, -1]), int(chs[0, -1])
+    G, Hs = float(Gq) * ginv, float(Hq) * hinv
+    root = G * G / (Hs + lam) if Hs + lam > 0.0 else 0.0
+    gm, hm = H[:, MISSING_BIN, 0], H[:, MISSING_BIN, 1]
+    GLq = np.zeros((d, 2 * MAX_BIN), np.int64)
+    HLq = np.zeros((d, 2 * MAX_BIN), np.int64)
+    GLq[:, 1], HLq[:, 1] = gm, hm                                   # b = -1, default left
+    GLq[:, 2::2], HLq[:, 2::2] = cg[:, :-1], chs[:, :-1]            # b = 0 .. 254, missing right
+    GLq[:, 3::2], HLq[:, 3::2] = cg[:, :-1] + gm[:, None], chs[:, :-1] + hm[:, None]  # missing left
+    GL = GLq.astype(np.float64) * ginv
+    HL = HLq.astype(np.float64) * hinv
+    GR = (Gq - GLq).astype(np.float64) * ginv
+    HR = (Hq - HLq).astype(np.float64) * hinv
+    dl, dr = HL + lam, HR + lam
+    with np.errstate(all="ignore"):
+        gain = (np.where(dl > 0.0, GL * GL / dl, 0.0) + np.where(dr > 0.0, GR * GR / dr, 0.0)) - root
+    b = (np.arange(2 * MAX_BIN) >> 1)[None, :] - 1
+    valid = (b < (nbins[:d, None] - 1)) & (HL >= mcw) & (HR >= mcw)
+    valid[:, 0] = False
+    if fmask is not None:
+        valid &= ((int(fmask) >> np.arange(d)) & 1).astype(bool)[:, None]
+    gain = np.where(valid, gain, -np.inf)
+    flat = int(np.argmax(gain))
+    f, k = divmod(flat, 2 * MAX_BIN)
+    return float(gain[f, k]), f, (k >> 1) - 1, int(GLq[f, k]), int(HLq[f, k]), Gq, Hq, k & 1
+
+
+def bins_go_right(v: np.ndarray, b, default_left) -> np.ndarray:
+    """The direction rule on bin bytes v: (v == 255) ? !default_left : v > b.  With default_left 0
+    it is v > b for every byte (b <= 254 wherever 255 is the missing slot)."""
+    v = np.asarray(v).astype(np.int64)
+    return np.where((v == MISSING_BIN) & (np.asarray(default_left) != 0), False, v > b)
+
+
 def build_tree(bins: np.ndarray, q: np.ndarray, cuts: np.ndarray, nbins: np.ndarray, depth: int, lam: float,
-               mcw: float, gamma: float, eta: float, gscale: float, hscale: float, comm=None, fmasks=None):
+               mcw: float, gamma: float, eta: float, gscale: float, hscale: float, comm=None, fmasks=None,
+               missing: bool = False):
     """Grow one depth-`depth` heap tree.  Returns (TreeArrays, leaf index per row [n]).
-    ``fmasks``: uint32 [2^depth - 1] allowed-feature bits per heap node (feature_masks), or None."""
+    ``fmasks``: uint32 [2^depth - 1] allowed-feature bits per heap node (feature_masks), or None.
+    ``missing``: byte 255 of ``bins`` is the missing slot; TreeArrays.default_left is filled."""
     n = bins.shape[0]
     d = int(len(nbins))
     ginv, hinv = 1.0 / gscale, 1.0 / hscale
@@ -186,6 +270,7 @@ def build_tree(bins: np.ndarray, q: np.ndarray, cuts: np.ndarray, nbins: np.ndar
     binv = np.full(ni, 255, np.int32)
     thr = np.full(ni, np.inf, np.float32)
     gain = np.zeros(ni, np.float64)
+    dleft = np.zeros(ni, np.uint8)
     ng = np.zeros(2 * nl - 1, np.int64)
     nh = np.zeros(2 * nl - 1, np.int64)
     node = np.zeros(n, np.int64)  # index within the level
@@ -200,21 +285,26 @@ def build_tree(bins: np.ndarray, q: np.ndarray, cuts: np.ndarray, nbins: np.ndar
         right = np.zeros(n, bool)
         for k in range(nn):
             hid = h0 + k
-            g_, f, b, GLq, HLq, Gq, Hq = best_split(Hl[k], nbins, ginv, hinv, lam, mcw,
-                                                        None if fmasks is None else int(fmasks[hid]))
+            fm = None if fmasks is None else int(fmasks[hid])
+            if missing:
+                g_, f, b, GLq, HLq, Gq, Hq, dl = best_split(Hl[k], nbins, ginv, hinv, lam, mcw, fm, True)
+            else:
+                (g_, f, b, GLq, HLq, Gq, Hq), dl = best_split(Hl[k], nbins, ginv, hinv, lam, mcw, fm), 0
             if hid == 0:
                 ng[0], nh[0] = Gq, Hq
             split = accepts_split(g_, gamma)
             lc, rc = 2 * hid + 1, 2 * hid + 2
             if split:
-                feat[hid], binv[hid], thr[hid], gain[hid] = f, b, cuts[f, b], g_
+                feat[hid], binv[hid], thr[hid], gain[hid] = f, b, (cuts[f, b] if b >= 0 else -np.inf), g_
+                dleft[hid] = dl
                 ng[lc], nh[lc], ng[rc], nh[rc] = GLq, HLq, Gq - GLq, Hq - HLq
                 sel = node == k
-                right |= sel & (bins[:, f] > b)
+                right |= sel & (bins_go_right(bins[:, f], b, dl) if missing else (bins[:, f] > b))
             else:
                 ng[lc], nh[lc], ng[rc], nh[rc] = Gq, Hq, 0, 0
         node = 2 * node + right.astype(np.int64)
-    return TreeArrays(feat, binv, thr, gain, leaf_values(ng, nh, depth, ginv, hinv, lam, mcw, eta)), node
+    return TreeArrays(feat, binv, thr, gain, leaf_values(ng, nh, depth, ginv, hinv, lam, mcw, eta),
+                      dleft if missing else None), node
 
 
 def accepts_split(gain: float, gamma: float) -> bool:
@@ -419,8 +509,9 @@ def ap_q(margin: np.ndarray, y: np.ndarray) -> int:
 
 
 def predict_margin(X: np.ndarray, feat: np.ndarray, thr: np.ndarray, leaf: np.ndarray, depth: int,
-                   base_margin: float = 0.0) -> np.ndarray:
-    """X [n, d] float32; feat/thr [T, ni]; leaf [T, nl].  float32 margins (sum in tree order)."""
+                   base_margin: float = 0.0, default_left: np.ndarray | None = None) -> np.ndarray:
+    """X [n, d] float32; feat/thr [T, ni]; leaf [T, nl].  float32 margins (sum in tree order).
+    ``default_left`` [T, ni] (None: all zero): a NaN goes left at a node where it is set."""
     X = np.asarray(X, dtype=np.float32)
     n = X.shape[0]
     out = np.full(n, np.float32(base_margin), dtype=np.float32)
@@ -431,15 +522,18 @@ def predict_margin(X: np.ndarray, feat: np.ndarray, thr: np.ndarray, leaf: np.nd
             f = feat[t][node]
             xv = X[rows, np.maximum(f, 0)]
             right = (f >= 0) & ~(xv < thr[t][node])
+            if default_left is not None:
+                right &= ~(np.isnan(xv) & (default_left[t][node] != 0))
             node = 2 * node + 1 + right
         out = (out + leaf[t][node - ((1 << depth) - 1)]).astype(np.float32)
     return out
 
 
 def predict_margin_bins(bins: np.ndarray, feat: np.ndarray, binv: np.ndarray, leaf: np.ndarray, depth: int,
-                        base_margin: float = 0.0) -> np.ndarray:
+                        base_margin: float = 0.0, default_left: np.ndarray | None = None) -> np.ndarray:
     """The device margin walk (gbdt.hip gbdt_margin_kernel) on binned rows: a row goes right at a
-    node when its bin of the node's feature exceeds the split bin.  float32, summed in tree order."""
+    node when its bin of the node's feature exceeds the split bin.  float32, summed in tree order.
+    ``default_left`` [T, ni] (None: all zero): byte 255 goes left at a node where it is set."""
     bins = np.asarray(bins)
     n = bins.shape[0]
     out = np.full(n, np.float32(base_margin), dtype=np.float32)
@@ -450,6 +544,8 @@ def predict_margin_bins(bins: np.ndarray, feat: np.ndarray, binv: np.ndarray, le
             f = feat[t][node]
             bv = bins[rows, np.maximum(f, 0)].astype(np.int64)
             right = (f >= 0) & (bv > binv[t][node])
+            if default_left is not None:
+                right &= ~((bv == MISSING_BIN) & (default_left[t][node] != 0))
             node = 2 * node + 1 + right
         out = (out + leaf[t][node - ((1 << depth) - 1)]).astype(np.float32)
     return out

@@ -661,7 +661,7 @@ class TreeInferenceEngine(_EngineBase):
 
         e = self.ens
         m = RG.predict_margin(_standardize(X, self.mean, self.scale), e.feat, e.thr, e.leaf, e.depth,
-                              e.base_margin).astype(np.float64)
+                              e.base_margin, getattr(e, "default_left", None)).astype(np.float64)
         return 1.0 / (1.0 + np.exp(-m)), m
 
     def _predict_device(self, X: np.ndarray):
@@ -735,7 +735,7 @@ class TreeInferenceEngine(_EngineBase):
 
         e = self.ens
         return RG.predict_margin(_standardize(X, self.mean, self.scale), e.feat, e.thr, e.leaf, e.depth,
-                                 e.base_margin).astype(np.float64)
+                                 e.base_margin, getattr(e, "default_left", None)).astype(np.float64)
 
     def expected_value(self) -> float:
         return float(self.ens.base_margin)

@@ -82,7 +82,8 @@ def run(settings: Settings | None = None, model_type: str = "logistic", cv_folds
     miss = missing_report(X, names)
     say({k: v for k, v in miss.items() if v} or "no missing values")
     if any(miss.values()):
-        raise ValueError("missing feature values; impute before training")
+        raise ValueError("missing feature values; impute before training (this entry point's scaler and SMOTE "
+                         'have no NaN semantics; GBDTClassifier(missing_policy="learn") learns from them)')
     say("Splitting dataset (Train 80% / Test 20%)...")
     mode = s.split
     if mode == "auto":  # the sklearn split is a host argsort: past a few million rows use K3
