@@ -209,6 +209,8 @@ def knn_topk(Q: torch.Tensor, C: torch.Tensor, k: int = 5, self_offset: int = -1
         m.knn_topk3(ptr(Qp), ptr(Qhl), mq_pad, mq, ptr(Cp), ptr(Chl), ptr(tmax), mc_pad, mc, int(self_offset),
                     int(k), ptr(idx), ptr(score), ptr(ws_s), ptr(ws_i), ns, s)
     if want_dist:
+        if _operands is not None:  # the engine's own scores q.c - 0.5||c||^2 (tests)
+            _operands.update(score=score)
         qn = (Q[:, :30].double() ** 2).sum(1, keepdim=True)
         return idx, (qn - 2.0 * score.double()).float()
     return idx
