@@ -759,15 +759,51 @@ struct SplitOut {
 // Same gain arithmetic and validity tests.  The node's `bin` gets the walk's word: b for a
 // missing-right split, 0x200 | (b + 1) for a default-left one (goes_right); thr of b = -1 is -inf,
 // so x < thr is false for every non-NaN x and the fp32 walk agrees with the binned one.
-template <bool MISS>
+//
+// MONO (monotone constraints, xgboost's TreeEvaluator in fp64; reference_gbdt's module docstring):
+// bit f of `inc` / `dec` = the score may only rise / fall with feature f.  Every heap node carries
+// weight bounds [lo, hi] in two double [2^(D+1) - 1] arrays: a level-0 block takes -inf / +inf
+// without reading and stores them for node 0, every block stores its children's.  A side's weight is
+// w = clamp(H < mcw || H <= 0 ? 0 : -G / (H + lambda), lo, hi), its term -(2 G w + (H + lambda) w w)
+// (G^2 / (H + lambda) where nothing clamps), the gain (term(L) + term(R)) - term(node), and a
+// candidate on a constrained feature also needs wl <= wr (inc) or wl >= wr (dec).  The argmax carries
+// what it always did: thread 0 recomputes the winner's weights from its (GLq, HLq) with the same
+// expressions -- the same bits -- and hands mid = (wl + wr) / 2 to the children.  Without MONO the
+// pack MA is empty and the kernel is the code and the arguments it was.
+struct MonoArgs {
+  uint32_t inc, dec;  // disjoint feature bits
+  double* lo;         // [heap]
+  double* hi;
+};
+__device__ __forceinline__ double mono_weight(double G, double H, double lambda, double mcw, double lo, double hi) {
+#pragma clang fp contract(off)
+  double w = 0.0;
+  if (!(H < mcw || H <= 0.0)) w = -G / (H + lambda);
+  return w < lo ? lo : (w > hi ? hi : w);
+}
+__device__ __forceinline__ double mono_term(double G, double H, double lambda, double w) {
+#pragma clang fp contract(off)
+  const double dn = H + lambda;
+  return dn > 0.0 ? -(2.0 * G * w + dn * w * w) : 0.0;
+}
+template <bool MISS, bool MONO = false, typename... MA>
 __global__ __launch_bounds__(kHistThreads) void gbdt_split_kernel(
     unsigned long long* __restrict__ hist, const int64_t* __restrict__ gcnt, int level, int d,
     const int* __restrict__ nbins, const float* __restrict__ cuts, double ginv, double hinv,
     double lambda, double min_child_weight, double gamma, int* __restrict__ tfeat,
     int* __restrict__ tbin, float* __restrict__ tthr, double* __restrict__ tgain,
-    long long* __restrict__ ng, long long* __restrict__ nh, const uint32_t* __restrict__ fmask) {
+    long long* __restrict__ ng, long long* __restrict__ nh, const uint32_t* __restrict__ fmask, MA... ma) {
 #pragma clang fp contract(off)
+  static_assert(sizeof...(MA) == (MONO ? 1 : 0), "tail: one MonoArgs with MONO");
   const int node = heap_first(level) + blockIdx.x;
+  [[maybe_unused]] uint32_t inc = 0u, dec = 0u;
+  [[maybe_unused]] double lo = -__builtin_inf(), hi = __builtin_inf();
+  [[maybe_unused]] double *blo = nullptr, *bhi = nullptr;
+  if constexpr (MONO) {
+    const MonoArgs a = (ma, ...);
+    inc = a.inc; dec = a.dec; blo = a.lo; bhi = a.hi;
+    if (level != 0) { lo = blo[node]; hi = bhi[node]; }
+  }
   // column subsampling: bit f of fmask[node] = feature f may be picked (null: every feature).  A
   // masked-out feature loses only its candidate: its wave still stores a derived node's H = parent -
   // sibling (the children subtract from it) and feature 0's wave still publishes the node totals.
@@ -820,7 +856,10 @@ __global__ __launch_bounds__(kHistThreads) void gbdt_split_kernel(
     // a term G^2 / (H + lambda) whose denominator is <= 0 counts as 0 (lambda = 0 with an empty or
     // zero-Hessian side: 0/0 or G^2/0 otherwise) -- the oracle's rule, reference_gbdt.py
     const double dn = Hs + lambda;
-    const double root = dn > 0.0 ? G * G / dn : 0.0;
+    double root;
+    if constexpr (MONO) root = mono_term(G, Hs, lambda, mono_weight(G, Hs, lambda, min_child_weight, lo, hi));
+    else root = dn > 0.0 ? G * G / dn : 0.0;
+    [[maybe_unused]] const bool up = (inc >> f) & 1u, down = (dec >> f) & 1u;  // wave-uniform
     const int nb = nbins[f];
     double best = -1.0e300;
     int bb = 0x7fffffff;
@@ -831,9 +870,17 @@ __global__ __launch_bounds__(kHistThreads) void gbdt_split_kernel(
       const double GL = (double)GLq * ginv, HL = (double)HLq * hinv;
       const double GR = (double)(Gq - GLq) * ginv, HR = (double)(Hq - HLq) * hinv;
       if (in_range && HL >= min_child_weight && HR >= min_child_weight) {
-        const double dl = HL + lambda, dr = HR + lambda;
-        const double gain = ((dl > 0.0 ? GL * GL / dl : 0.0) + (dr > 0.0 ? GR * GR / dr : 0.0)) - root;
-        if (gain > best) { best = gain; bb = key; bgl = GLq; bhl = HLq; }
+        if constexpr (MONO) {
+          const double wl = mono_weight(GL, HL, lambda, min_child_weight, lo, hi);
+          const double wr = mono_weight(GR, HR, lambda, min_child_weight, lo, hi);
+          const double gain = (mono_term(GL, HL, lambda, wl) + mono_term(GR, HR, lambda, wr)) - root;
+          const bool ok = up ? wl <= wr : (down ? wl >= wr : true);
+          if (ok && gain > best) { best = gain; bb = key; bgl = GLq; bhl = HLq; }
+        } else {
+          const double dl = HL + lambda, dr = HR + lambda;
+          const double gain = ((dl > 0.0 ? GL * GL / dl : 0.0) + (dr > 0.0 ? GR * GR / dr : 0.0)) - root;
+          if (gain > best) { best = gain; bb = key; bgl = GLq; bhl = HLq; }
+        }
       }
     };
     if constexpr (MISS) consider(lane == 0, 1, Gm, Hm);  // b = -1: the missing rows alone go left
@@ -895,6 +942,23 @@ __global__ __launch_bounds__(kHistThreads) void gbdt_split_kernel(
       ng[r] = 0; nh[r] = 0;
     }
     if (node == 0) { ng[0] = Gq; nh[0] = Hq; }
+    if constexpr (MONO) {
+      // children inherit; a split on a constrained feature puts mid between them.  The winner's
+      // weights come from its integer sums by the candidate's own expressions.
+      double ll = lo, lh = hi, rl = lo, rh = hi;
+      const bool up = split && ((inc >> bf) & 1u), down = split && ((dec >> bf) & 1u);
+      if (up || down) {
+        const long long GLq = fgl[bf], HLq = fhl[bf];
+        const double wl = mono_weight((double)GLq * ginv, (double)HLq * hinv, lambda, min_child_weight, lo, hi);
+        const double wr = mono_weight((double)(Gq - GLq) * ginv, (double)(Hq - HLq) * hinv, lambda,
+                                      min_child_weight, lo, hi);
+        const double mid = (wl + wr) / 2.0;
+        if (up) { lh = mid; rl = mid; } else { ll = mid; rh = mid; }
+      }
+      blo[l] = ll; bhi[l] = lh;
+      blo[r] = rl; bhi[r] = rh;
+      if (node == 0) { blo[0] = lo; bhi[0] = hi; }
+    }
   }
 }
 
@@ -1206,9 +1270,12 @@ __global__ __launch_bounds__(256) void gbdt_round_init_kernel(unsigned long long
 // ---- leaves ----------------------------------------------------------------------------------
 // xgboost CalcWeight: 0 if H < min_child_weight or H <= 0, else -G / (H + lambda); the stored
 // leaf value is eta * weight.
+// blo / bhi (both or neither; null: no bounds): the heap's weight bounds of a monotone fit -- the
+// weight is clamped into its leaf node's [lo, hi] after the zero rule.
 __global__ void gbdt_leaf_kernel(const long long* __restrict__ ng, const long long* __restrict__ nh,
                                  int depth, double ginv, double hinv, double lambda,
-                                 double min_child_weight, double eta, float* __restrict__ leaf) {
+                                 double min_child_weight, double eta, float* __restrict__ leaf,
+                                 const double* __restrict__ blo, const double* __restrict__ bhi) {
 #pragma clang fp contract(off)
   const int nl = 1 << depth;
   for (int i = threadIdx.x; i < nl; i += blockDim.x) {
@@ -1216,6 +1283,10 @@ __global__ void gbdt_leaf_kernel(const long long* __restrict__ ng, const long lo
     const double G = (double)ng[node] * ginv, H = (double)nh[node] * hinv;
     double w = 0.0;
     if (!(H < min_child_weight || H <= 0.0)) w = -G / (H + lambda);
+    if (blo != nullptr) {
+      const double lo = blo[node], hi = bhi[node];
+      w = w < lo ? lo : (w > hi ? hi : w);
+    }
     leaf[i] = (float)(eta * w);
   }
 }
@@ -1614,9 +1685,26 @@ void launch_gbdt_split(unsigned long long* hist, const int64_t* gcnt, int level,
                        const float* cuts, double ginv, double hinv, double lambda,
                        double min_child_weight, double gamma, int* feat, int* bin, float* thr,
                        double* gain, long long* ng, long long* nh, hipStream_t stream, const uint32_t* fmask,
-                       bool missing) {
+                       bool missing, uint32_t mono_inc, uint32_t mono_dec, double* mono_lo, double* mono_hi) {
   if (level < 0 || (1 << level) > kGBMaxNodes + 1) throw std::runtime_error("gbdt_split: level out of range");
   if (d < 1 || d > kGBMaxFeat) throw std::runtime_error("gbdt_split: bad feature count");
+  if (mono_inc & mono_dec) throw std::runtime_error("gbdt_split: monotone masks overlap");
+  if (((mono_inc | mono_dec) >> d) != 0u) throw std::runtime_error("gbdt_split: monotone mask bit at or above d");
+  if ((mono_inc | mono_dec) != 0u) {
+    if (mono_lo == nullptr || mono_hi == nullptr)
+      throw std::runtime_error("gbdt_split: monotone masks need both bounds arrays");
+    const MonoArgs ma{mono_inc, mono_dec, mono_lo, mono_hi};
+    if (missing)
+      gbdt_split_kernel<true, true><<<1 << level, kHistThreads, 0, stream>>>(
+          hist, gcnt, level, d, nbins, cuts, ginv, hinv, lambda, min_child_weight, gamma, feat, bin, thr, gain, ng,
+          nh, fmask, ma);
+    else
+      gbdt_split_kernel<false, true><<<1 << level, kHistThreads, 0, stream>>>(
+          hist, gcnt, level, d, nbins, cuts, ginv, hinv, lambda, min_child_weight, gamma, feat, bin, thr, gain, ng,
+          nh, fmask, ma);
+    check_launch("gbdt_split");
+    return;
+  }
   if (missing)
     gbdt_split_kernel<true><<<1 << level, kHistThreads, 0, stream>>>(hist, gcnt, level, d, nbins, cuts, ginv, hinv,
                                                                      lambda, min_child_weight, gamma, feat, bin,
@@ -1659,8 +1747,12 @@ void launch_gbdt_round_init(unsigned long long* hist, int64_t hist_words, int64_
 }
 
 void launch_gbdt_leaf(const long long* ng, const long long* nh, int depth, double ginv, double hinv,
-                      double lambda, double min_child_weight, double eta, float* leaf, hipStream_t stream) {
-  gbdt_leaf_kernel<<<1, 256, 0, stream>>>(ng, nh, depth, ginv, hinv, lambda, min_child_weight, eta, leaf);
+                      double lambda, double min_child_weight, double eta, float* leaf, hipStream_t stream,
+                      const double* mono_lo, const double* mono_hi) {
+  if ((mono_lo == nullptr) != (mono_hi == nullptr))
+    throw std::runtime_error("gbdt_leaf: monotone bounds need both arrays or neither");
+  gbdt_leaf_kernel<<<1, 256, 0, stream>>>(ng, nh, depth, ginv, hinv, lambda, min_child_weight, eta, leaf, mono_lo,
+                                          mono_hi);
   check_launch("gbdt_leaf");
 }
 

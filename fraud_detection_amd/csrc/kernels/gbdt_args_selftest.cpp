@@ -1,6 +1,6 @@
 // Host-side self-test of the GBDT launchers whose signatures grew for missing_policy="learn"
 // (gbdt.hip launch_gbdt_bin / launch_gbdt_split / launch_gbdt_predict, quantile.hip
-// launch_quantile_select): every argument check must throw BEFORE anything is launched, whatever the
+// launch_quantile_select) and for monotone constraints (launch_gbdt_split / launch_gbdt_leaf): every argument check must throw BEFORE anything is launched, whatever the
 // new trailing arguments are, and the old call forms (trailing arguments left out) must still
 // compile.  Built with -fsanitize=address,undefined on the host side (tools/sanitize_host.sh); it
 // needs no GPU: a call that passes its checks either launches or reports the missing device as a
@@ -79,6 +79,31 @@ int main() {
                                missing);
       });
   }
+  // monotone constraints (launch_gbdt_split / launch_gbdt_leaf trailing arguments): the masks are
+  // checked against each other, against d and against the bounds pointers before any launch
+  for (bool missing : {false, true}) {
+    auto split = [&](int d, uint32_t inc, uint32_t dec, double* lo, double* hi) {
+      fdx::launch_gbdt_split(hist.data(), gc.data(), 0, d, i32.data(), f32.data(), 1.0, 1.0, 1.0, 1.0, 0.0, i32.data(),
+                             i32.data(), f32.data(), f64.data(), i64.data(), i64.data(), nullptr, nullptr, missing, inc,
+                             dec, lo, hi);
+    };
+    expect_refused("gbdt_split overlapping masks", "monotone masks overlap",
+                   [&] { split(4, 0x3u, 0x2u, f64.data(), f64.data()); });
+    expect_refused("gbdt_split inc bit = d", "mask bit at or above d", [&] { split(4, 0x10u, 0x1u, f64.data(), f64.data()); });
+    expect_refused("gbdt_split dec bit 31", "mask bit at or above d",
+                   [&] { split(30, 0x1u, 0x80000000u, f64.data(), f64.data()); });
+    expect_refused("gbdt_split masks, no bounds", "need both bounds arrays", [&] { split(4, 0x1u, 0x2u, nullptr, nullptr); });
+    expect_refused("gbdt_split masks, lo only", "need both bounds arrays", [&] { split(4, 0x1u, 0x0u, f64.data(), nullptr); });
+    expect_refused("gbdt_split masks, hi only", "need both bounds arrays", [&] { split(4, 0x0u, 0x2u, nullptr, f64.data()); });
+    // the earlier checks still come first, whatever the masks are
+    expect_refused("gbdt_split bad d with masks", "bad feature count", [&] { split(31, 0x1u, 0x1u, nullptr, nullptr); });
+  }
+  expect_refused("gbdt_leaf lo only", "both arrays or neither", [&] {
+    fdx::launch_gbdt_leaf(i64.data(), i64.data(), 3, 1.0, 1.0, 1.0, 1.0, 0.1, f32.data(), nullptr, f64.data(), nullptr);
+  });
+  expect_refused("gbdt_leaf hi only", "both arrays or neither", [&] {
+    fdx::launch_gbdt_leaf(i64.data(), i64.data(), 3, 1.0, 1.0, 1.0, 1.0, 0.1, f32.data(), nullptr, nullptr, f64.data());
+  });
   for (const uint8_t* dleft : {static_cast<const uint8_t*>(nullptr), static_cast<const uint8_t*>(u8.data())}) {
     for (int depth : {0, 9})
       expect_refused("gbdt_predict bad depth", "depth must be in [1, 8]", [&] {
@@ -132,6 +157,10 @@ int main() {
       expect_checked("gbdt_bin, valid", [&] {
         fdx::launch_gbdt_bin(f32.data(), 4, 32, 30, f32.data(), i32.data(), u8.data(), nullptr, missing);
       });
+    // disjoint masks below d with both bounds, and the leaf's old call form: past the checks
+    expect_checked("gbdt_leaf, old form", [&] {
+      fdx::launch_gbdt_leaf(i64.data(), i64.data(), 3, 1.0, 1.0, 1.0, 1.0, 0.1, f32.data(), nullptr);
+    });
   }
   if (failures) {
     std::printf("gbdt_args_selftest: %d failure(s)\n", failures);

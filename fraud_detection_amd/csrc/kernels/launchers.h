@@ -468,7 +468,12 @@ void launch_gbdt_split(unsigned long long* hist, const int64_t* gcnt, int level,
                        double min_child_weight, double gamma, int* feat, int* bin, float* thr,
                        double* gain, long long* ng, long long* nh, hipStream_t stream,
                        const uint32_t* fmask = nullptr,  // [heap] allowed-feature bits per node; null: all
-                       bool missing = false);  // slot 255 = the missing rows; `bin` gets split words (gbdt.hip)
+                       bool missing = false,  // slot 255 = the missing rows; `bin` gets split words (gbdt.hip)
+                       // monotone constraints: disjoint feature bits below d (score may only rise / fall
+                       // with the feature) and, with any bit set, the heap's weight bounds, double
+                       // [2^(D+1) - 1] each, read at `level` and written for the children (gbdt.hip)
+                       uint32_t mono_inc = 0, uint32_t mono_dec = 0, double* mono_lo = nullptr,
+                       double* mono_hi = nullptr);
 // row-major [n][32] bins -> feature-major [d][ldt] (the partition's per-row feature reads)
 void launch_gbdt_transpose(const uint8_t* bins, int64_t n, int d, uint8_t* binsT, int64_t ldt, hipStream_t stream);
 void launch_gbdt_partition(const uint8_t* binsT, int64_t ldt, const int* ridx, const uint8_t* nid, int64_t n,
@@ -479,7 +484,9 @@ void launch_gbdt_partition(const uint8_t* binsT, int64_t ldt, const int* ridx, c
 void launch_gbdt_round_init(unsigned long long* hist, int64_t hist_words, int64_t* seg, int64_t* gcnt, int64_t n,
                             int64_t n_global, hipStream_t stream, int64_t* node_r, int n_nodes);
 void launch_gbdt_leaf(const long long* ng, const long long* nh, int depth, double ginv, double hinv,
-                      double lambda, double min_child_weight, double eta, float* leaf, hipStream_t stream);
+                      double lambda, double min_child_weight, double eta, float* leaf, hipStream_t stream,
+                      // a monotone fit's weight bounds (both or neither): the leaf weight is clamped
+                      const double* mono_lo = nullptr, const double* mono_hi = nullptr);
 void launch_gbdt_margin(const uint8_t* binsT, int64_t ldt, int64_t n, const int* feat, const int* bin,
                         const float* leaf, int depth, float* margin, const uint8_t* label, float spw, float gscale,
                         float hscale, uint32_t* gh, hipStream_t stream);

@@ -26,6 +26,42 @@ HIST_ENTRIES = MAX_FEAT * MAX_BIN * 2
 PART_BLOCKS = int(os.environ.get("FDX_GBDT_PART_BLOCKS", "2048"))
 
 
+def normalize_monotone(mc):
+    """xgboost's ``monotone_constraints`` in one of its forms -> None, a tuple of ints in {-1, 0, 1}
+    (one per feature) or a dict {feature index: sign} with int keys >= 0.  Accepted: a sequence of
+    ints, the string form "(1,0,-1)", a dict.  Anything else is a ValueError."""
+    def sign(v):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or int(v) not in (-1, 0, 1):
+            raise ValueError(f"monotone_constraints: every entry must be the integer -1, 0 or 1, got {v!r}")
+        return int(v)
+
+    if mc is None:
+        return None
+    if isinstance(mc, str):
+        body = mc.strip()
+        if body.startswith("(") and body.endswith(")"):
+            body = body[1:-1]
+        try:
+            mc = [int(tok) for tok in body.split(",") if tok.strip()]
+        except ValueError:
+            raise ValueError(f"monotone_constraints: cannot parse {mc!r}; the string form is '(1,0,-1)'") from None
+    if isinstance(mc, dict):
+        out = {}
+        for k, v in mc.items():
+            if isinstance(k, str) and k.strip().lstrip("+-").isdigit():
+                k = int(k)
+            if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or int(k) < 0:
+                raise ValueError(f"monotone_constraints: dict keys are feature indices >= 0, got {k!r} "
+                                 "(feature names are resolved by the train entry point)")
+            if int(k) in out:
+                raise ValueError(f"monotone_constraints: feature {int(k)} is named twice")
+            out[int(k)] = sign(v)
+        return out
+    if isinstance(mc, (list, tuple, np.ndarray)):
+        return tuple(sign(v) for v in (mc.tolist() if isinstance(mc, np.ndarray) else mc))
+    raise ValueError(f"monotone_constraints must be a sequence of ints, a string like '(1,0,-1)' or a dict, got {mc!r}")
+
+
 @dataclass
 class GBDTParams:
     """xgboost.XGBClassifier parameter names and defaults used by train_model.py:69-80."""
@@ -51,12 +87,17 @@ class GBDTParams:
     # "learn": NaN gets a bin slot of its own and every split learns which side it goes to
     # (xgboost's sparsity-aware split finding; reference_gbdt's module docstring has the rules).
     missing_policy: str = "last_bin"
+    # xgboost's monotone_constraints: per feature +1 (the score never falls as the feature rises), -1
+    # (never rises) or 0.  A sequence of d ints, the string "(1,0,-1)" or {feature index: sign};
+    # None or all zero: unconstrained, launch for launch (fit_binned has the rules).
+    monotone_constraints: tuple | dict | str | None = None
 
     MISSING_POLICIES = ("last_bin", "learn")
     # fields a checkpoint signature names only off their defaults (older checkpoints resume): the
     # sampling fields and, added the same way, the missing policy
     SAMPLING_DEFAULTS = {"subsample": 1.0, "colsample_bytree": 1.0, "colsample_bylevel": 1.0,
-                         "colsample_bynode": 1.0, "seed": 0, "missing_policy": "last_bin"}
+                         "colsample_bynode": 1.0, "seed": 0, "missing_policy": "last_bin",
+                         "monotone_constraints": None}
 
     @property
     def colsampled(self) -> bool:
@@ -70,7 +111,22 @@ class GBDTParams:
     def learn_missing(self) -> bool:
         return self.missing_policy == "learn"
 
+    def monotone_signs(self, d: int):
+        """int64 [d] signs of a d-feature fit, or None when nothing is constrained."""
+        mc = normalize_monotone(self.monotone_constraints)
+        if mc is None:
+            return None
+        if isinstance(mc, dict):
+            bad = [k for k in mc if k >= d]
+            if bad:
+                raise ValueError(f"monotone_constraints: feature index {bad[0]} is out of range for {d} features")
+            mc = tuple(mc.get(f, 0) for f in range(d))
+        if len(mc) != d:
+            raise ValueError(f"monotone_constraints has {len(mc)} entries, the fit has {d} features")
+        return np.asarray(mc, np.int64) if any(mc) else None
+
     def validate(self):
+        self.monotone_constraints = normalize_monotone(self.monotone_constraints)
         if self.missing_policy not in self.MISSING_POLICIES:
             raise ValueError(f"missing_policy must be one of {self.MISSING_POLICIES}, got {self.missing_policy!r}")
         for name in ("subsample", "colsample_bytree", "colsample_bylevel", "colsample_bynode"):
@@ -278,6 +334,9 @@ class _Workspace:
         self.slots = torch.empty(native().gbdt_hist_slot_words(), dtype=torch.int64, device=dev)
         self.ng = torch.zeros(nheap, dtype=torch.int64, device=dev)
         self.nh = torch.zeros(nheap, dtype=torch.int64, device=dev)
+        # weight bounds per heap node of a monotone fit (gbdt_split writes them level by level)
+        self.blo = torch.full((nheap,), -np.inf, dtype=torch.float64, device=dev)
+        self.bhi = torch.full((nheap,), np.inf, dtype=torch.float64, device=dev)
 
 
 # ---- per-round evaluation and early stopping -------------------------------------------------
@@ -608,7 +667,20 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
     "logloss" and "error" become weighted means and stay exact integers
     (reference_gbdt.eval_record_weighted; EvalRecord.weight_q is the denominator); the stop rule
     compares the integer numerators, the denominator being constant.  "auc" and "aucpr" with
-    evaluation weights raise NotImplementedError (their kernels count pairs and tie groups)."""
+    evaluation weights raise NotImplementedError (their kernels count pairs and tie groups).
+
+    Monotone constraints (``monotone_constraints`` of GBDTParams, xgboost's TreeEvaluator in fp64;
+    reference_gbdt's module docstring has the rules): every heap node carries weight bounds, a side's
+    weight is clamped into them, a candidate on a constrained feature must order its children's
+    weights, and the children of such a split meet at the mean of their weights.  Only the split scan
+    and the leaf weights change, both fp64 functions of the integer histogram sums, so trees stay
+    bitwise deterministic and equal to the oracle's, and a constrained tree is an ordinary tree for
+    every walk, explainer and model file.  Every tree -- and so the fp32 margin, fp32 addition being
+    monotone in each argument -- is monotone in every constrained feature over its non-NaN values.
+    The bounds live in two static workspace arrays (the hipGraph path replays them); sampling,
+    weights, learned missing directions, evaluation, the row hole, data parallelism (the histograms
+    are all-reduced before the scan) and checkpoints compose unchanged.  The length is checked
+    against the feature count here; all zero is the unconstrained fit, launch for launch."""
     p = (params or GBDTParams()).validate()
     cuts_np, nbins = cuts
     d = int(len(nbins))
@@ -642,6 +714,9 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
     dist = comm is not None and comm.world_size > 1
     sub_on, seed = p.subsample != 1.0, int(p.seed)
     learn = p.learn_missing
+    mono = p.monotone_signs(d)  # [d] signs or None
+    mono_inc = 0 if mono is None else int(sum(1 << f for f in range(d) if mono[f] > 0))
+    mono_dec = 0 if mono is None else int(sum(1 << f for f in range(d) if mono[f] < 0))
     if learn and int(np.max(nbins, initial=0)) > MAX_BIN - 1:
         raise ValueError('missing_policy="learn": byte 255 is the missing slot, the cuts may hold at most 255 '
                          "real bins per feature (quantile_cuts(..., missing=True))")
@@ -658,7 +733,9 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
                                   p.colsample_bynode) if p.colsampled else None
     # the policy is named only where it is not the default: a "last_bin" model serialises as before
     ens_kw = dict(depth=D, cuts=cuts_np, nbins=nbins, base_score=p.base_score,
-                  params={**{k: v for k, v in p.__dict__.items() if k != "missing_policy" or learn}, "seed": seed})
+                  params={**{k: v for k, v in p.__dict__.items()
+                             if k not in ("missing_policy", "monotone_constraints") or (k == "missing_policy" and learn)},
+                          "seed": seed, **({} if mono is None else {"monotone_constraints": [int(c) for c in mono]})})
     req = _eval_request(eval_set, eval_metric, early_stopping_rounds, hl, checkpoint,
                         comm is not None and comm.world_size > 1, T)
     ev = None
@@ -698,7 +775,9 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
         # they existed still resume
         dflt = p.SAMPLING_DEFAULTS
         sig_params = {k: v for k, v in p.__dict__.items()
-                      if k != "n_estimators" and not (k in dflt and v == dflt[k])}
+                      if k not in ("n_estimators", "monotone_constraints") and not (k in dflt and v == dflt[k])}
+        if mono is not None:  # the resolved signs, whatever form they were given in
+            sig_params["monotone_constraints"] = [int(c) for c in mono]
         # Which global rows the fit draws for is part of a sampled fit's configuration.  Every rank
         # must compute the SAME signature (rank 0 writes the checkpoint, all ranks load it), so
         # under data parallelism it names every rank's offset, not this rank's.
@@ -746,7 +825,7 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
                 q[~R.row_sample_mask(seed, t, keep + row_offset, p.subsample)] = 0
             tr, node = R.build_tree(b, q, cuts_np, nbins, D, p.reg_lambda, p.min_child_weight, p.gamma,
                                     p.learning_rate, gscale, hscale, comm, None if fmasks is None else fmasks[t],
-                                    learn)
+                                    learn, mono)
             feat[t], binv[t], thr[t], gain[t], leaf[t] = tr.feat, tr.bin, tr.thr, tr.gain, tr.leaf
             if learn:
                 dleft[t] = tr.default_left
@@ -836,6 +915,9 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
         cur = 0
         fmask_arg = () if fm_dev is None else (ptr(fm_dev[t]),)  # the round's [ni] mask row; none: every feature
         miss_arg = {"missing": True} if learn else {}  # the scan learns the missing slot's side; o_bin gets words
+        # monotone fit: the sign masks and the heap's weight bounds (static pointers)
+        mono_arg = {} if mono is None else {"mono_inc": mono_inc, "mono_dec": mono_dec, "mono_lo": ptr(ws.blo),
+                                            "mono_hi": ptr(ws.bhi)}
         for level in range(D):
             h0, nn = (1 << level) - 1, 1 << level
             if level == 0 and prev is not None:
@@ -849,7 +931,7 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
                 comm.all_reduce_(ws.hist[h0 * HIST_ENTRIES:(h0 + nn) * HIST_ENTRIES])
             m.gbdt_split(ptr(ws.hist), ptr(ws.gcnt), level, d, ptr(nt), ptr(ct), ginv, hinv, lam, mcw, gam,
                          ptr(o_feat), ptr(o_bin), ptr(o_thr), ptr(o_gain), ptr(ws.ng), ptr(ws.nh), st, *fmask_arg,
-                         **miss_arg)
+                         **miss_arg, **mono_arg)
             if level == D - 1:
                 break  # leaves: the margin walk and gbdt_leaf (split-kernel child sums) need no partition
             if n_fit:
@@ -864,7 +946,8 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
                 ws.gcnt[c0:c0 + 2 * nn].zero_()
             if dist:
                 comm.all_reduce_(ws.gcnt[c0:c0 + 2 * nn])
-        m.gbdt_leaf(ptr(ws.ng), ptr(ws.nh), D, ginv, hinv, lam, mcw, float(p.learning_rate), ptr(o_leaf), st)
+        m.gbdt_leaf(ptr(ws.ng), ptr(ws.nh), D, ginv, hinv, lam, mcw, float(p.learning_rate), ptr(o_leaf), st,
+                    *((ptr(ws.blo), ptr(ws.bhi)) if mono is not None else ()))
         if n and not defer_margin and grad_next and wt is not None and sub_on:
             m.gbdt_margin_sampled_weighted(ptr(binsT), ldt, n, ptr(o_feat), ptr(o_bin), ptr(o_leaf), D, ptr(margin),
                                            ptr(y), ptr(wt), spw, gscale, hscale, ptr(ws.gh), seed, t + 1, row_offset,

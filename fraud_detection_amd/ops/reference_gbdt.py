@@ -35,6 +35,22 @@ every function here is what it was):
   (v == 255) ? !default_left : v > bin.  x < -inf is false for every non-NaN x, so the b = -1
   split sends exactly the missing rows left in both walks.
 
+Monotone constraints (``mono=(cons, lo, hi)`` / ``monotone=cons``; default off, and off means every
+function here is what it was): cons[f] in {-1, 0, +1}, every heap node carries weight bounds
+[lo, hi], the root (-inf, +inf) -- xgboost's TreeEvaluator in fp64:
+
+* weight w(G, H) = clamp(H < mcw or H <= 0 ? 0 : -G / (H + l), lo, hi), the clamp after the zero rule
+  and written w < lo ? lo : (w > hi ? hi : w);
+* term(G, H, w) = -(2 G w + (H + l) w w) where H + l > 0, else 0 (unclamped it is G^2 / (H + l));
+* a candidate's gain is (term(L, wl) + term(R, wr)) - term(node, w(node)), wl / wr the children's
+  weights under the NODE's bounds; on a feature with c > 0 it needs wl <= wr, with c < 0 wl >= wr, on
+  top of the unchanged validity tests.  Same tie order, same acceptance rule;
+* children inherit [lo, hi]; with mid = (wl + wr) / 2 of the winning candidate, c > 0 sets
+  hi[left] = lo[right] = mid and c < 0 sets lo[left] = hi[right] = mid; a pass-through node hands its
+  bounds to both children;
+* leaf = float32(eta * w(G, H)) under the leaf node's bounds.
+With ``missing`` the missing rows count in whichever side the candidate puts them.
+
 xgboost itself is not installed in this image, so parity with xgboost is "unpinned"; the
 semantics above follow xgboost's hist updater (train_model.py:69-80 uses XGBClassifier).
 """
@@ -184,14 +200,16 @@ class TreeArrays:
 
 
 def best_split(H: np.ndarray, nbins: np.ndarray, ginv: float, hinv: float, lam: float, mcw: float,
-               fmask: int | None = None, missing: bool = False):
+               fmask: int | None = None, missing: bool = False, mono=None):
     """H: int64 [d, 256, 2] of one node.  Returns (gain, feature, bin, GLq, HLq, Gq, Hq).
     ``fmask``: bit f set = feature f may be picked (None: all).  The node totals come from feature
     0's sums whether or not feature 0 is allowed; with no valid allowed split the gain is -inf.
     ``missing``: slot 255 holds the missing rows' sums and the scan learns their side (module
-    docstring); the return value gains default_left as its eighth element and bin may be -1."""
+    docstring); the return value gains default_left as its eighth element and bin may be -1.
+    ``mono``: (cons [d] in {-1, 0, 1}, lo, hi) -- the node's weight bounds and the features' signs
+    (module docstring); None is the unconstrained scan, untouched."""
     if missing:
-        return _best_split_missing(H, nbins, ginv, hinv, lam, mcw, fmask)
+        return _best_split_missing(H, nbins, ginv, hinv, lam, mcw, fmask, mono)
     d = H.shape[0]
     cg = np.cumsum(H[:, :, 0], axis=1)
     chs = np.cumsum(H[:, :, 1], axis=1)
@@ -207,6 +225,9 @@ def best_split(H: np.ndarray, nbins: np.ndarray, ginv: float, hinv: float, lam: 
         gain = (np.where(dl > 0.0, GL * GL / dl, 0.0) + np.where(dr > 0.0, GR * GR / dr, 0.0)) - root
     b = np.arange(MAX_BIN)[None, :]
     valid = (b < (nbins[:d, None] - 1)) & (HL >= mcw) & (HR >= mcw)
+    if mono is not None:
+        gain, ok = _mono_gain(GL, HL, GR, HR, G, Hs, lam, mcw, mono)
+        valid &= ok
     if fmask is not None:
         valid &= ((int(fmask) >> np.arange(d)) & 1).astype(bool)[:, None]
     gain = np.where(valid, gain, -np.inf)
@@ -215,7 +236,56 @@ def best_split(H: np.ndarray, nbins: np.ndarray, ginv: float, hinv: float, lam: 
     return float(gain[f, bb]), f, bb, int(cg[f, bb]), int(chs[f, bb]), Gq, Hq
 
 
-def _best_split_missing(H, nbins, ginv, hinv, lam, mcw, fmask):
+def mono_weight(G: float, H: float, lam: float, mcw: float, lo: float, hi: float) -> float:
+    """clamp(H < mcw or H <= 0 ? 0 : -G / (H + lam), lo, hi) on Python floats (IEEE fp64)."""
+    w = 0.0 if (H < mcw or H <= 0.0) else -G / (H + lam)
+    return lo if w < lo else (hi if w > hi else w)
+
+
+def mono_term(G: float, H: float, lam: float, w: float) -> float:
+    dn = H + lam
+    return -(2.0 * G * w + dn * w * w) if dn > 0.0 else 0.0
+
+
+def _mono_weight_v(G, H, lam, mcw, lo, hi):
+    with np.errstate(all="ignore"):
+        w = np.where((H < mcw) | (H <= 0.0), 0.0, -G / (H + lam))
+    return np.where(w < lo, lo, np.where(w > hi, hi, w))
+
+
+def _mono_term_v(G, H, lam, w):
+    dn = H + lam
+    with np.errstate(all="ignore"):
+        return np.where(dn > 0.0, -(2.0 * G * w + dn * w * w), 0.0)
+
+
+def _mono_gain(GL, HL, GR, HR, G, Hs, lam, mcw, mono):
+    """(gain table, sign test) of candidates with fp64 side sums [d, K] under mono = (cons, lo, hi);
+    the expression order is gbdt.hip's (gbdt_split_kernel<MISS, true>)."""
+    cons, lo, hi = mono
+    lo, hi = float(lo), float(hi)
+    root = mono_term(G, Hs, lam, mono_weight(G, Hs, lam, mcw, lo, hi))
+    wl = _mono_weight_v(GL, HL, lam, mcw, lo, hi)
+    wr = _mono_weight_v(GR, HR, lam, mcw, lo, hi)
+    gain = (_mono_term_v(GL, HL, lam, wl) + _mono_term_v(GR, HR, lam, wr)) - root
+    c = np.asarray(cons, np.int64)[: GL.shape[0], None]
+    return gain, np.where(c > 0, wl <= wr, np.where(c < 0, wl >= wr, True))
+
+
+def mono_children(c: int, lo: float, hi: float, GLq: int, HLq: int, Gq: int, Hq: int, ginv: float, hinv: float,
+                  lam: float, mcw: float):
+    """(lo_left, hi_left, lo_right, hi_right) below a split on a feature of sign c whose left child
+    has the sums (GLq, HLq): the weights are recomputed from the integers as the candidate's were."""
+    lo, hi = float(lo), float(hi)
+    if c == 0:
+        return lo, hi, lo, hi
+    wl = mono_weight(float(GLq) * ginv, float(HLq) * hinv, lam, mcw, lo, hi)
+    wr = mono_weight(float(Gq - GLq) * ginv, float(Hq - HLq) * hinv, lam, mcw, lo, hi)
+    mid = (wl + wr) / 2.0
+    return (lo, mid, mid, hi) if c > 0 else (mid, hi, lo, mid)
+
+
+def _best_split_missing(H, nbins, ginv, hinv, lam, mcw, fmask, mono=None):
     """best_split with a learned side for slot 255.  Candidate (b, dl) sits at column 2 (b + 1) + dl
     of a [d, 512] gain table -- the tie order -- so one argmax picks the lowest feature, then the
     lowest b (-1 first), then default_left 0.  Column 0 (b = -1, nothing left) is no candidate."""
@@ -241,6 +311,9 @@ def _best_split_missing(H, nbins, ginv, hinv, lam, mcw, fmask):
     b = (np.arange(2 * MAX_BIN) >> 1)[None, :] - 1
     valid = (b < (nbins[:d, None] - 1)) & (HL >= mcw) & (HR >= mcw)
     valid[:, 0] = False
+    if mono is not None:
+        gain, ok = _mono_gain(GL, HL, GR, HR, G, Hs, lam, mcw, mono)
+        valid &= ok
     if fmask is not None:
         valid &= ((int(fmask) >> np.arange(d)) & 1).astype(bool)[:, None]
     gain = np.where(valid, gain, -np.inf)
@@ -258,10 +331,11 @@ def bins_go_right(v: np.ndarray, b, default_left) -> np.ndarray:
 
 def build_tree(bins: np.ndarray, q: np.ndarray, cuts: np.ndarray, nbins: np.ndarray, depth: int, lam: float,
                mcw: float, gamma: float, eta: float, gscale: float, hscale: float, comm=None, fmasks=None,
-               missing: bool = False):
+               missing: bool = False, monotone=None):
     """Grow one depth-`depth` heap tree.  Returns (TreeArrays, leaf index per row [n]).
     ``fmasks``: uint32 [2^depth - 1] allowed-feature bits per heap node (feature_masks), or None.
-    ``missing``: byte 255 of ``bins`` is the missing slot; TreeArrays.default_left is filled."""
+    ``missing``: byte 255 of ``bins`` is the missing slot; TreeArrays.default_left is filled.
+    ``monotone``: [d] signs in {-1, 0, 1} (None: unconstrained); every node gets weight bounds."""
     n = bins.shape[0]
     d = int(len(nbins))
     ginv, hinv = 1.0 / gscale, 1.0 / hscale
@@ -273,6 +347,10 @@ def build_tree(bins: np.ndarray, q: np.ndarray, cuts: np.ndarray, nbins: np.ndar
     dleft = np.zeros(ni, np.uint8)
     ng = np.zeros(2 * nl - 1, np.int64)
     nh = np.zeros(2 * nl - 1, np.int64)
+    blo = bhi = None
+    if monotone is not None:
+        monotone = np.asarray(monotone, np.int64)
+        blo, bhi = np.full(2 * nl - 1, -np.inf), np.full(2 * nl - 1, np.inf)
     node = np.zeros(n, np.int64)  # index within the level
     for level in range(depth):
         nn = 1 << level
@@ -286,10 +364,11 @@ def build_tree(bins: np.ndarray, q: np.ndarray, cuts: np.ndarray, nbins: np.ndar
         for k in range(nn):
             hid = h0 + k
             fm = None if fmasks is None else int(fmasks[hid])
+            mono = None if monotone is None else (monotone, blo[hid], bhi[hid])
             if missing:
-                g_, f, b, GLq, HLq, Gq, Hq, dl = best_split(Hl[k], nbins, ginv, hinv, lam, mcw, fm, True)
+                g_, f, b, GLq, HLq, Gq, Hq, dl = best_split(Hl[k], nbins, ginv, hinv, lam, mcw, fm, True, mono)
             else:
-                (g_, f, b, GLq, HLq, Gq, Hq), dl = best_split(Hl[k], nbins, ginv, hinv, lam, mcw, fm), 0
+                (g_, f, b, GLq, HLq, Gq, Hq), dl = best_split(Hl[k], nbins, ginv, hinv, lam, mcw, fm, mono=mono), 0
             if hid == 0:
                 ng[0], nh[0] = Gq, Hq
             split = accepts_split(g_, gamma)
@@ -302,8 +381,11 @@ def build_tree(bins: np.ndarray, q: np.ndarray, cuts: np.ndarray, nbins: np.ndar
                 right |= sel & (bins_go_right(bins[:, f], b, dl) if missing else (bins[:, f] > b))
             else:
                 ng[lc], nh[lc], ng[rc], nh[rc] = Gq, Hq, 0, 0
+            if monotone is not None:
+                blo[lc], bhi[lc], blo[rc], bhi[rc] = mono_children(
+                    int(monotone[f]) if split else 0, blo[hid], bhi[hid], GLq, HLq, Gq, Hq, ginv, hinv, lam, mcw)
         node = 2 * node + right.astype(np.int64)
-    return TreeArrays(feat, binv, thr, gain, leaf_values(ng, nh, depth, ginv, hinv, lam, mcw, eta),
+    return TreeArrays(feat, binv, thr, gain, leaf_values(ng, nh, depth, ginv, hinv, lam, mcw, eta, blo, bhi),
                       dleft if missing else None), node
 
 
@@ -313,13 +395,16 @@ def accepts_split(gain: float, gamma: float) -> bool:
 
 
 def leaf_values(ng: np.ndarray, nh: np.ndarray, depth: int, ginv: float, hinv: float, lam: float, mcw: float,
-                eta: float) -> np.ndarray:
-    """float32 [2^depth] leaf values from the heap's int64 node sums ng / nh (leaves at 2^depth - 1 ..)."""
+                eta: float, lo=None, hi=None) -> np.ndarray:
+    """float32 [2^depth] leaf values from the heap's int64 node sums ng / nh (leaves at 2^depth - 1 ..).
+    ``lo`` / ``hi``: [heap] weight bounds of a monotone fit (the weight is clamped into them)."""
     ni, nl = (1 << depth) - 1, 1 << depth
     leaf = np.zeros(nl, np.float32)
     for i in range(nl):
         G, H = float(ng[ni + i]) * ginv, float(nh[ni + i]) * hinv
         w = 0.0 if (H < mcw or H <= 0.0) else -G / (H + lam)
+        if lo is not None:
+            w = float(lo[ni + i]) if w < lo[ni + i] else (float(hi[ni + i]) if w > hi[ni + i] else w)
         leaf[i] = np.float32(eta * w)
     return leaf
 

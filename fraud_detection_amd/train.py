@@ -52,10 +52,33 @@ def _shard(idx: np.ndarray, comm) -> np.ndarray:
     return idx[comm.rank::comm.world_size]
 
 
+def parse_gbdt_monotone(spec: str | None, names) -> dict | None:
+    """``--gbdt-monotone "Amount=1,V14=-1"`` -> {feature index: sign}, the names resolved against the
+    table's feature columns.  None / empty: no constraints.  An unknown or repeated name, or a sign
+    other than -1, 0, 1, is a ValueError."""
+    if spec is None or not spec.strip():
+        return None
+    names = list(names)
+    out = {}
+    for item in spec.split(","):
+        name, eq, val = item.partition("=")
+        name, val = name.strip(), val.strip()
+        if not eq or not name:
+            raise ValueError(f"--gbdt-monotone: expected NAME=SIGN, got {item.strip()!r}")
+        if name not in names:
+            raise ValueError(f"--gbdt-monotone: the table has no feature column {name!r}")
+        if val not in ("-1", "0", "1", "+1"):
+            raise ValueError(f"--gbdt-monotone: the sign of {name!r} must be -1, 0 or 1, got {val!r}")
+        if names.index(name) in out:
+            raise ValueError(f"--gbdt-monotone: {name!r} is named twice")
+        out[names.index(name)] = int(val)
+    return out
+
+
 def run(settings: Settings | None = None, model_type: str = "logistic", cv_folds: int = 5, model_dir: str = "models",
         verbose: bool = True, cfg: TrainConfig | None = None, comm=None, gbdt_eval_metric=None,
         gbdt_early_stopping: int | None = None, gbdt_subsample: float = 1.0, gbdt_colsample_bytree: float = 1.0,
-        gbdt_seed: int = 0) -> dict:
+        gbdt_seed: int = 0, gbdt_monotone: str | None = None) -> dict:
     """Single process, or data parallel when ``comm`` spans several ranks (torchrun: one rank per
     GPU).  Every rank reads the table and derives the same split; each fits on its strided shard
     with RCCL all-reduced statistics, so all ranks hold the same model; rank 0 writes artifacts.
@@ -65,7 +88,12 @@ def run(settings: Settings | None = None, model_type: str = "logistic", cv_folds
     rounds and the final fit's round count land in the summary under "gbdt_eval".
 
     ``gbdt_subsample`` / ``gbdt_colsample_bytree`` / ``gbdt_seed``: stochastic boosting of the GBDT
-    family (ops/gbdt.GBDTParams), in every CV fold and in the final fit alike."""
+    family (ops/gbdt.GBDTParams), in every CV fold and in the final fit alike.
+
+    ``gbdt_monotone``: "Amount=1,V14=-1" -- monotone constraints by column name (parse_gbdt_monotone),
+    in every CV fold and in the final fit; standardisation divides by a positive scale, so a sign on
+    the raw column is the same sign on the standardised one.  The chosen signs land in the summary
+    under "gbdt_monotone"."""
     s = settings or Settings.load()
     comm = comm if (comm is not None and comm.world_size > 1) else None
     lead = comm is None or comm.rank == 0
@@ -114,10 +142,13 @@ def run(settings: Settings | None = None, model_type: str = "logistic", cv_folds
     if model_type == "gbdt":
         from .ops.gbdt import GBDTParams
 
+        gbdt_mono = parse_gbdt_monotone(gbdt_monotone, names)
         gbdt_params = GBDTParams(subsample=gbdt_subsample, colsample_bytree=gbdt_colsample_bytree,
-                                 seed=gbdt_seed).validate()
+                                 seed=gbdt_seed, monotone_constraints=gbdt_mono).validate()
     elif (gbdt_subsample, gbdt_colsample_bytree, gbdt_seed) != (1.0, 1.0, 0):
         raise ValueError("--gbdt-subsample / --gbdt-colsample-bytree / --gbdt-seed need --model gbdt")
+    elif gbdt_monotone:
+        raise ValueError("--gbdt-monotone needs --model gbdt")
     cv_scores = []
     from dataclasses import asdict
 
@@ -232,6 +263,8 @@ def run(settings: Settings | None = None, model_type: str = "logistic", cv_folds
     if gbdt_params is not None and gbdt_params.sampled:
         summary["gbdt_sampling"] = {"subsample": gbdt_params.subsample,
                                     "colsample_bytree": gbdt_params.colsample_bytree, "seed": gbdt_params.seed}
+    if gbdt_params is not None and gbdt_params.monotone_constraints:
+        summary["gbdt_monotone"] = {names[f]: c for f, c in sorted(gbdt_params.monotone_constraints.items()) if c}
     try:
         summary["registered_version"] = _track(s, model_type, res, summary, paths, Xte, names, say)
     except Exception as e:  # noqa: BLE001 - tracking is best effort (reference train_model.py:165-166)
@@ -286,7 +319,9 @@ def _job_signature(s, model_type, cv_folds, split_mode, cfg: dict, shape, comm, 
                             world=1 if comm is None else comm.world_size,
                             # only when sampling is on: records written before it existed still match
                             **({"gbdt_sampling": [gbdt_params.subsample, gbdt_params.colsample_bytree, gbdt_params.seed]}
-                               if gbdt_params is not None and gbdt_params.sampled else {}))
+                               if gbdt_params is not None and gbdt_params.sampled else {}),
+                            **({"gbdt_monotone": sorted(gbdt_params.monotone_constraints.items())}
+                               if gbdt_params is not None and gbdt_params.monotone_constraints else {}))
 
 
 def _cross_validate(model_type, cfg, folds, take, comm, mode: str, progress: _Progress | None = None,
@@ -378,6 +413,8 @@ def _track(s: Settings, model_type, res, summary, paths, Xte, names, say):
             mlf.log_metric("cv_auc_std", summary["cv_auc_std"])
         for k, v in (summary.get("gbdt_sampling") or {}).items():
             mlf.log_param(f"gbdt_{k}", v)
+        if summary.get("gbdt_monotone"):
+            mlf.log_param("gbdt_monotone", ",".join(f"{k}={v}" for k, v in summary["gbdt_monotone"].items()))
         ge = summary.get("gbdt_eval")
         if ge:
             mlf.log_param("gbdt_eval_metric", ",".join(ge["metrics"]))
@@ -433,6 +470,9 @@ def main(argv=None):
     ap.add_argument("--gbdt-colsample-bytree", type=float, default=1.0,
                     help="feature fraction every tree draws (1.0: all features)")
     ap.add_argument("--gbdt-seed", type=int, default=0, help="seed of the row / feature draws")
+    ap.add_argument("--gbdt-monotone", default=None, metavar="NAME=SIGN,...",
+                    help='monotone constraints by column name, e.g. "Amount=1,V14=-1": the score never falls (1) or '
+                         "never rises (-1) as the column grows; an unknown name is an error")
     a = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO)
     comm = None
@@ -450,7 +490,8 @@ def main(argv=None):
         out = run(st, model_type=a.model, cv_folds=a.cv_folds, model_dir=a.model_dir, comm=comm,
                   gbdt_eval_metric=a.gbdt_eval_metric.split(",") if a.gbdt_eval_metric else None,
                   gbdt_early_stopping=a.gbdt_early_stopping, gbdt_subsample=a.gbdt_subsample,
-                  gbdt_colsample_bytree=a.gbdt_colsample_bytree, gbdt_seed=a.gbdt_seed)
+                  gbdt_colsample_bytree=a.gbdt_colsample_bytree, gbdt_seed=a.gbdt_seed,
+                  gbdt_monotone=a.gbdt_monotone)
     finally:
         if comm is not None:
             comm.close()
