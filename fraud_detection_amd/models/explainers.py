@@ -144,9 +144,14 @@ def wls_operator(Z: np.ndarray, w: np.ndarray):
     return A, zM
 
 
-def _link(v, link):
+def _link(v, link, eps: float = 1e-12):
+    """Coalition values and f0 are means of probabilities, clipped to [eps, 1 - eps] before the
+    logit.  f(x) is NOT clipped like that: shap applies the link to the model output as it is, and
+    the device kernels return the model's own logit (a served LR reaches +-33, beyond
+    logit(1 - 1e-12) = 27.6).  Where only a probability is at hand (FunctionKernelExplainer) fx is
+    clipped at fp64's resolution of 1 - p, eps = 2^-53, merely to stay finite."""
     if link == "logit":
-        v = np.clip(v, 1e-12, 1 - 1e-12)
+        v = np.clip(v, eps, 1 - eps)
         return np.log(v / (1 - v))
     return v
 
@@ -173,7 +178,9 @@ def kernelshap_reference(X: np.ndarray, a: np.ndarray, bias: float, B: np.ndarra
         f = (1.0 / (1.0 + np.exp(-L))).mean(1)
         f0 = float((1.0 / (1.0 + np.exp(-c))).mean())
         fx = 1.0 / (1.0 + np.exp(-(X @ a + bias)))
-        f, f0, fx = _link(f, link), float(_link(np.asarray(f0), link)), _link(fx, link)
+        f, f0 = _link(f, link), float(_link(np.asarray(f0), link))
+        if link == "logit":
+            fx = X @ a + bias            # the model's logit itself, unclipped (as the kernels)
     y = f - f0
     delta = fx - f0
     phi = np.empty((X.shape[0], d))
@@ -314,7 +321,7 @@ def kernelshap_tree_reference(Xs: np.ndarray, Bs: np.ndarray, ens, Z: np.ndarray
         R1 = (Zt[:, :, None] & xw[:, e][:, None, None]) | (~Zt[:, :, None] & bw[:, None, :])  # [T, S, nb]
         f[e] = sig(_margins_from_bits(R1, ens)).mean(1)
     if link == "logit":
-        f, f0, fx = _link(f, link), float(_link(np.asarray(f0), link)), _link(fx, link)
+        f, f0, fx = _link(f, link), float(_link(np.asarray(f0), link)), mx   # fx: the margin, unclipped
     return _project(f, f0, fx, A, zM), fx, f0
 
 
@@ -538,7 +545,7 @@ class FunctionKernelExplainer:
             f[e0:e0 + per] = out.mean(2)
         f, fx = f.cpu().numpy(), fx.cpu().numpy()
         if self.link == "logit":
-            f, f0, fx = _link(f, "logit"), float(_link(np.asarray(f0), "logit")), _link(fx, "logit")
+            f, f0, fx = _link(f, "logit"), float(_link(np.asarray(f0), "logit")), _link(fx, "logit", 2.0 ** -53)
         return _project(f, f0, fx, self.A, self.zM), fx, f0
 
 
