@@ -953,16 +953,19 @@ PYBIND11_MODULE(_fdx_native, m) {
   });
   m.def("gbdt_split", [](u hist, u gcnt, int level, int d, u nbins, u cuts, double ginv, double hinv, double lam,
                          double mcw, double gamma, u feat, u bin, u thr, u gain, u ng, u nh, u s, u fmask,
-                         bool missing, uint32_t mono_inc, uint32_t mono_dec, u mono_lo, u mono_hi) {
+                         bool missing, uint32_t mono_inc, uint32_t mono_dec, u mono_lo, u mono_hi,
+                         const std::vector<uint32_t>& inter_groups, u inter_path) {
     fdx::launch_gbdt_split(P<unsigned long long>(hist), P<const int64_t>(gcnt), level, d, P<const int>(nbins),
                            P<const float>(cuts), ginv, hinv, lam, mcw, gamma, P<int>(feat), P<int>(bin), P<float>(thr),
                            P<double>(gain), P<long long>(ng), P<long long>(nh), S(s), P<const uint32_t>(fmask),
-                           missing, mono_inc, mono_dec, P<double>(mono_lo), P<double>(mono_hi));
+                           missing, mono_inc, mono_dec, P<double>(mono_lo), P<double>(mono_hi), inter_groups,
+                           P<uint32_t>(inter_path));
   }, py::arg("hist"), py::arg("gcnt"), py::arg("level"), py::arg("d"), py::arg("nbins"), py::arg("cuts"),
      py::arg("ginv"), py::arg("hinv"), py::arg("lam"), py::arg("mcw"), py::arg("gamma"), py::arg("feat"),
      py::arg("bin"), py::arg("thr"), py::arg("gain"), py::arg("ng"), py::arg("nh"), py::arg("s"),
      py::arg("fmask") = 0, py::arg("missing") = false, py::arg("mono_inc") = 0, py::arg("mono_dec") = 0,
-     py::arg("mono_lo") = 0, py::arg("mono_hi") = 0);
+     py::arg("mono_lo") = 0, py::arg("mono_hi") = 0, py::arg("inter_groups") = std::vector<uint32_t>{},
+     py::arg("inter_path") = 0);
   m.def("gbdt_transpose", [](u bins, int64_t n, int d, u binsT, int64_t ldt, u s) {
     fdx::launch_gbdt_transpose(P<const uint8_t>(bins), n, d, P<uint8_t>(binsT), ldt, S(s));
   });

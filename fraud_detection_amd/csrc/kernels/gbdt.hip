@@ -770,11 +770,33 @@ struct SplitOut {
 // what it always did: thread 0 recomputes the winner's weights from its (GLq, HLq) with the same
 // expressions -- the same bits -- and hands mid = (wl + wr) / 2 to the children.  Without MONO the
 // pack MA is empty and the kernel is the code and the arguments it was.
+//
+// INTER (interaction constraints, xgboost's FeatureInteractionConstraintHost as a function of the
+// path; reference_gbdt's module docstring): an InterArgs in the pack MA, after the MonoArgs if both
+// are there.  `path` holds one word per heap node, the split features of the node's ancestors: a
+// level-0 block takes 0 without reading and stores it for node 0, every block stores its children's,
+// path | 1 << feature below a split and path itself below a pass-through.  With an empty path every
+// feature is allowed; otherwise allowed = path | the union of the groups g with path inside g, ANDed
+// into the word that gates fgain[f] (fmask, when there is one, first).  Nothing else changes: a
+// feature that is not allowed loses only its candidate, as under column subsampling.  The group
+// words travel by value in the kernel arguments, so the launcher checks them and a captured graph
+// replays them.  Without an InterArgs the kernel is the code and the arguments it was.
 struct MonoArgs {
   uint32_t inc, dec;  // disjoint feature bits
   double* lo;         // [heap]
   double* hi;
 };
+constexpr int kGBMaxGroups = 32;
+struct InterArgs {
+  uint32_t n;                // groups in use
+  uint32_t g[kGBMaxGroups];  // feature bits of each group
+  uint32_t* path;            // [heap]
+};
+template <typename T, typename A0, typename... A>
+__host__ __device__ __forceinline__ T pack_get(A0 a0, A... a) {
+  if constexpr (std::is_same_v<T, A0>) return a0;
+  else return pack_get<T>(a...);
+}
 __device__ __forceinline__ double mono_weight(double G, double H, double lambda, double mcw, double lo, double hi) {
 #pragma clang fp contract(off)
   double w = 0.0;
@@ -794,20 +816,36 @@ __global__ __launch_bounds__(kHistThreads) void gbdt_split_kernel(
     int* __restrict__ tbin, float* __restrict__ tthr, double* __restrict__ tgain,
     long long* __restrict__ ng, long long* __restrict__ nh, const uint32_t* __restrict__ fmask, MA... ma) {
 #pragma clang fp contract(off)
-  static_assert(sizeof...(MA) == (MONO ? 1 : 0), "tail: one MonoArgs with MONO");
+  constexpr bool INTER = (std::is_same_v<MA, InterArgs> || ...);
+  static_assert(sizeof...(MA) == (MONO ? 1 : 0) + (INTER ? 1 : 0), "tail: [MonoArgs with MONO] [InterArgs]");
   const int node = heap_first(level) + blockIdx.x;
   [[maybe_unused]] uint32_t inc = 0u, dec = 0u;
   [[maybe_unused]] double lo = -__builtin_inf(), hi = __builtin_inf();
   [[maybe_unused]] double *blo = nullptr, *bhi = nullptr;
   if constexpr (MONO) {
-    const MonoArgs a = (ma, ...);
+    const MonoArgs a = pack_get<MonoArgs>(ma...);
     inc = a.inc; dec = a.dec; blo = a.lo; bhi = a.hi;
     if (level != 0) { lo = blo[node]; hi = bhi[node]; }
   }
   // column subsampling: bit f of fmask[node] = feature f may be picked (null: every feature).  A
   // masked-out feature loses only its candidate: its wave still stores a derived node's H = parent -
   // sibling (the children subtract from it) and feature 0's wave still publishes the node totals.
-  const uint32_t allowed = fmask ? fmask[node] : 0xffffffffu;
+  uint32_t eligible = fmask ? fmask[node] : 0xffffffffu;
+  [[maybe_unused]] uint32_t pth = 0u;
+  [[maybe_unused]] uint32_t* ipath = nullptr;
+  if constexpr (INTER) {
+    const InterArgs ia = pack_get<InterArgs>(ma...);
+    ipath = ia.path;
+    if (level != 0) pth = ipath[node];
+    if (pth != 0u) {  // block-uniform
+      uint32_t open = pth;
+#pragma unroll
+      for (int i = 0; i < kGBMaxGroups; ++i)
+        if ((uint32_t)i < ia.n && (pth & ~ia.g[i]) == 0u) open |= ia.g[i];
+      eligible &= open;
+    }
+  }
+  const uint32_t allowed = eligible;
   const int lane = lane_id(), wv = wave_id();
   constexpr int kW = kHistThreads / kWave;
   long long* H = reinterpret_cast<long long*>(hist) + (int64_t)node * kHistEntries;
@@ -958,6 +996,12 @@ __global__ __launch_bounds__(kHistThreads) void gbdt_split_kernel(
       blo[l] = ll; bhi[l] = lh;
       blo[r] = rl; bhi[r] = rh;
       if (node == 0) { blo[0] = lo; bhi[0] = hi; }
+    }
+    if constexpr (INTER) {
+      const uint32_t below = pth | (split ? 1u << bf : 0u);
+      ipath[l] = below;
+      ipath[r] = below;
+      if (node == 0) ipath[0] = 0u;
     }
   }
 }
@@ -1685,34 +1729,42 @@ void launch_gbdt_split(unsigned long long* hist, const int64_t* gcnt, int level,
                        const float* cuts, double ginv, double hinv, double lambda,
                        double min_child_weight, double gamma, int* feat, int* bin, float* thr,
                        double* gain, long long* ng, long long* nh, hipStream_t stream, const uint32_t* fmask,
-                       bool missing, uint32_t mono_inc, uint32_t mono_dec, double* mono_lo, double* mono_hi) {
+                       bool missing, uint32_t mono_inc, uint32_t mono_dec, double* mono_lo, double* mono_hi,
+                       const std::vector<uint32_t>& inter_groups, uint32_t* inter_path) {
   if (level < 0 || (1 << level) > kGBMaxNodes + 1) throw std::runtime_error("gbdt_split: level out of range");
   if (d < 1 || d > kGBMaxFeat) throw std::runtime_error("gbdt_split: bad feature count");
   if (mono_inc & mono_dec) throw std::runtime_error("gbdt_split: monotone masks overlap");
   if (((mono_inc | mono_dec) >> d) != 0u) throw std::runtime_error("gbdt_split: monotone mask bit at or above d");
-  if ((mono_inc | mono_dec) != 0u) {
-    if (mono_lo == nullptr || mono_hi == nullptr)
-      throw std::runtime_error("gbdt_split: monotone masks need both bounds arrays");
-    const MonoArgs ma{mono_inc, mono_dec, mono_lo, mono_hi};
-    if (missing)
-      gbdt_split_kernel<true, true><<<1 << level, kHistThreads, 0, stream>>>(
-          hist, gcnt, level, d, nbins, cuts, ginv, hinv, lambda, min_child_weight, gamma, feat, bin, thr, gain, ng,
-          nh, fmask, ma);
-    else
-      gbdt_split_kernel<false, true><<<1 << level, kHistThreads, 0, stream>>>(
-          hist, gcnt, level, d, nbins, cuts, ginv, hinv, lambda, min_child_weight, gamma, feat, bin, thr, gain, ng,
-          nh, fmask, ma);
-    check_launch("gbdt_split");
-    return;
+  const bool mono = (mono_inc | mono_dec) != 0u, inter = !inter_groups.empty();
+  if (mono && (mono_lo == nullptr || mono_hi == nullptr))
+    throw std::runtime_error("gbdt_split: monotone masks need both bounds arrays");
+  if (inter_groups.size() > (size_t)kGBMaxGroups)
+    throw std::runtime_error("gbdt_split: at most 32 interaction groups");
+  for (uint32_t g : inter_groups) {
+    if ((g >> d) != 0u) throw std::runtime_error("gbdt_split: interaction group bit at or above d");
+    if (g == 0u) throw std::runtime_error("gbdt_split: empty interaction group");
   }
-  if (missing)
-    gbdt_split_kernel<true><<<1 << level, kHistThreads, 0, stream>>>(hist, gcnt, level, d, nbins, cuts, ginv, hinv,
-                                                                     lambda, min_child_weight, gamma, feat, bin,
-                                                                     thr, gain, ng, nh, fmask);
-  else
-    gbdt_split_kernel<false><<<1 << level, kHistThreads, 0, stream>>>(hist, gcnt, level, d, nbins, cuts, ginv, hinv,
-                                                                      lambda, min_child_weight, gamma, feat, bin,
-                                                                      thr, gain, ng, nh, fmask);
+  if (inter && inter_path == nullptr) throw std::runtime_error("gbdt_split: interaction groups need the path array");
+  if (!inter && inter_path != nullptr) throw std::runtime_error("gbdt_split: a path array needs interaction groups");
+  const MonoArgs ma{mono_inc, mono_dec, mono_lo, mono_hi};
+  InterArgs ia{};
+  ia.n = (uint32_t)inter_groups.size();
+  for (size_t i = 0; i < inter_groups.size(); ++i) ia.g[i] = inter_groups[i];
+  ia.path = inter_path;
+  // <MISS, MONO> and the tail the instantiation takes: nothing, MonoArgs, InterArgs or both
+  auto go = [&](auto miss, auto mn, auto... tail) {
+    gbdt_split_kernel<decltype(miss)::value, decltype(mn)::value, decltype(tail)...>
+        <<<1 << level, kHistThreads, 0, stream>>>(hist, gcnt, level, d, nbins, cuts, ginv, hinv, lambda,
+                                                  min_child_weight, gamma, feat, bin, thr, gain, ng, nh, fmask, tail...);
+  };
+  auto by_tail = [&](auto miss) {
+    if (mono && inter) go(miss, std::true_type{}, ma, ia);
+    else if (mono) go(miss, std::true_type{}, ma);
+    else if (inter) go(miss, std::false_type{}, ia);
+    else go(miss, std::false_type{});
+  };
+  if (missing) by_tail(std::true_type{});
+  else by_tail(std::false_type{});
   check_launch("gbdt_split");
 }
 

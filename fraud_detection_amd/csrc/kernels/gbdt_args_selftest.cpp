@@ -1,8 +1,9 @@
 // Host-side self-test of the GBDT launchers whose signatures grew for missing_policy="learn"
 // (gbdt.hip launch_gbdt_bin / launch_gbdt_split / launch_gbdt_predict, quantile.hip
-// launch_quantile_select) and for monotone constraints (launch_gbdt_split / launch_gbdt_leaf): every argument check must throw BEFORE anything is launched, whatever the
-// new trailing arguments are, and the old call forms (trailing arguments left out) must still
-// compile.  Built with -fsanitize=address,undefined on the host side (tools/sanitize_host.sh); it
+// launch_quantile_select), for monotone constraints (launch_gbdt_split / launch_gbdt_leaf) and for
+// interaction constraints (launch_gbdt_split): every argument check must throw BEFORE anything is
+// launched, whatever the new trailing arguments are, and the old call forms (trailing arguments
+// left out) must still compile.  Built with -fsanitize=address,undefined on the host side (tools/sanitize_host.sh); it
 // needs no GPU: a call that passes its checks either launches or reports the missing device as a
 // std::runtime_error from check_launch, and both count as "got past the checks".
 #include <cstdint>
@@ -98,6 +99,29 @@ int main() {
     // the earlier checks still come first, whatever the masks are
     expect_refused("gbdt_split bad d with masks", "bad feature count", [&] { split(31, 0x1u, 0x1u, nullptr, nullptr); });
   }
+  // interaction constraints (launch_gbdt_split's last two arguments): the group masks are host
+  // values, checked against their number, against d and against the path pointer before any launch,
+  // with and without the monotone tail
+  std::vector<uint32_t> pathw(256, 0u);
+  for (bool missing : {false, true})
+    for (uint32_t inc : {0x0u, 0x1u}) {
+      auto split = [&](int d, const std::vector<uint32_t>& groups, uint32_t* path) {
+        fdx::launch_gbdt_split(hist.data(), gc.data(), 0, d, i32.data(), f32.data(), 1.0, 1.0, 1.0, 1.0, 0.0,
+                               i32.data(), i32.data(), f32.data(), f64.data(), i64.data(), i64.data(), nullptr, nullptr,
+                               missing, inc, 0u, f64.data(), f64.data(), groups, path);
+      };
+      expect_refused("gbdt_split 33 groups", "at most 32 interaction groups",
+                     [&] { split(4, std::vector<uint32_t>(33, 0x1u), pathw.data()); });
+      expect_refused("gbdt_split group bit = d", "interaction group bit at or above d",
+                     [&] { split(4, {0x3u, 0x10u}, pathw.data()); });
+      expect_refused("gbdt_split group bit 31", "interaction group bit at or above d",
+                     [&] { split(30, {0x80000000u}, pathw.data()); });
+      expect_refused("gbdt_split empty group", "empty interaction group", [&] { split(4, {0x3u, 0x0u}, pathw.data()); });
+      expect_refused("gbdt_split groups, no path", "need the path array", [&] { split(4, {0x3u}, nullptr); });
+      expect_refused("gbdt_split path, no groups", "needs interaction groups", [&] { split(4, {}, pathw.data()); });
+      // the earlier checks still come first, whatever the groups are
+      expect_refused("gbdt_split bad d with groups", "bad feature count", [&] { split(31, {0x3u}, nullptr); });
+    }
   expect_refused("gbdt_leaf lo only", "both arrays or neither", [&] {
     fdx::launch_gbdt_leaf(i64.data(), i64.data(), 3, 1.0, 1.0, 1.0, 1.0, 0.1, f32.data(), nullptr, f64.data(), nullptr);
   });

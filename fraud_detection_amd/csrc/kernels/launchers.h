@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 namespace fdx {
 
@@ -473,7 +474,12 @@ void launch_gbdt_split(unsigned long long* hist, const int64_t* gcnt, int level,
                        // with the feature) and, with any bit set, the heap's weight bounds, double
                        // [2^(D+1) - 1] each, read at `level` and written for the children (gbdt.hip)
                        uint32_t mono_inc = 0, uint32_t mono_dec = 0, double* mono_lo = nullptr,
-                       double* mono_hi = nullptr);
+                       double* mono_hi = nullptr,
+                       // interaction constraints: at most 32 non-empty groups of feature bits below d
+                       // (host values; they travel in the kernel arguments) and, with any group, the
+                       // heap's path words, uint32 [2^(D+1) - 1], read at `level` and written for the
+                       // children (gbdt.hip)
+                       const std::vector<uint32_t>& inter_groups = {}, uint32_t* inter_path = nullptr);
 // row-major [n][32] bins -> feature-major [d][ldt] (the partition's per-row feature reads)
 void launch_gbdt_transpose(const uint8_t* bins, int64_t n, int d, uint8_t* binsT, int64_t ldt, hipStream_t stream);
 void launch_gbdt_partition(const uint8_t* binsT, int64_t ldt, const int* ridx, const uint8_t* nid, int64_t n,

@@ -62,6 +62,48 @@ def normalize_monotone(mc):
     raise ValueError(f"monotone_constraints must be a sequence of ints, a string like '(1,0,-1)' or a dict, got {mc!r}")
 
 
+MAX_GROUPS = 32  # interaction groups of one fit (the split kernel takes their masks by value)
+
+
+def normalize_interaction(ic):
+    """xgboost's ``interaction_constraints`` in one of its forms -> None or a tuple of groups, each a
+    sorted tuple of feature indices >= 0; a group given twice is kept once, empty groups are dropped,
+    and nothing left is None.  Accepted: a nested sequence of ints, the string form
+    "[[0, 2], [1, 3, 4]]", None.  A non-integer, a bool, a negative index, a feature repeated inside
+    one group or anything unparsable is a ValueError."""
+    if ic is None:
+        return None
+    if isinstance(ic, str):
+        import json
+
+        try:
+            ic = json.loads(ic)
+        except ValueError:
+            raise ValueError(f"interaction_constraints: cannot parse {ic!r}; the string form is "
+                             "'[[0, 2], [1, 3, 4]]'") from None
+    if isinstance(ic, np.ndarray):
+        ic = ic.tolist()
+    if not isinstance(ic, (list, tuple)):
+        raise ValueError(f"interaction_constraints must be a list of lists of feature indices, a string like "
+                         f"'[[0, 2], [1, 3, 4]]' or None, got {ic!r}")
+    out = []
+    for g in ic:
+        if isinstance(g, np.ndarray):
+            g = g.tolist()
+        if not isinstance(g, (list, tuple)):
+            raise ValueError(f"interaction_constraints: every group must be a list of feature indices, got {g!r}")
+        for v in g:
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or int(v) < 0:
+                raise ValueError(f"interaction_constraints: feature indices are integers >= 0, got {v!r} "
+                                 "(feature names are resolved by the train entry point)")
+        grp = tuple(sorted(int(v) for v in g))
+        if len(set(grp)) != len(grp):
+            raise ValueError(f"interaction_constraints: a feature is repeated inside the group {list(g)!r}")
+        if grp and grp not in out:
+            out.append(grp)
+    return tuple(out) or None
+
+
 @dataclass
 class GBDTParams:
     """xgboost.XGBClassifier parameter names and defaults used by train_model.py:69-80."""
@@ -91,13 +133,18 @@ class GBDTParams:
     # (never rises) or 0.  A sequence of d ints, the string "(1,0,-1)" or {feature index: sign};
     # None or all zero: unconstrained, launch for launch (fit_binned has the rules).
     monotone_constraints: tuple | dict | str | None = None
+    # xgboost's interaction_constraints: groups of feature indices.  Below a path of split features
+    # a node may use the path's own features and every group that contains the whole path
+    # (reference_gbdt's module docstring has the rule).  A nested sequence of ints or the string
+    # "[[0, 2], [1, 3, 4]]"; None or no non-empty group: unconstrained, launch for launch.
+    interaction_constraints: tuple | list | str | None = None
 
     MISSING_POLICIES = ("last_bin", "learn")
     # fields a checkpoint signature names only off their defaults (older checkpoints resume): the
     # sampling fields and, added the same way, the missing policy
     SAMPLING_DEFAULTS = {"subsample": 1.0, "colsample_bytree": 1.0, "colsample_bylevel": 1.0,
                          "colsample_bynode": 1.0, "seed": 0, "missing_policy": "last_bin",
-                         "monotone_constraints": None}
+                         "monotone_constraints": None, "interaction_constraints": None}
 
     @property
     def colsampled(self) -> bool:
@@ -125,8 +172,22 @@ class GBDTParams:
             raise ValueError(f"monotone_constraints has {len(mc)} entries, the fit has {d} features")
         return np.asarray(mc, np.int64) if any(mc) else None
 
+    def interaction_masks(self, d: int):
+        """The groups of a d-feature fit as a list of uint32 masks (bit f = feature f), or None when
+        there is none."""
+        ic = normalize_interaction(self.interaction_constraints)
+        if ic is None:
+            return None
+        bad = [f for g in ic for f in g if f >= d]
+        if bad:
+            raise ValueError(f"interaction_constraints: feature index {bad[0]} is out of range for {d} features")
+        if len(ic) > MAX_GROUPS:
+            raise ValueError(f"interaction_constraints: {len(ic)} groups, at most {MAX_GROUPS} are supported")
+        return [int(sum(1 << f for f in g)) for g in ic]
+
     def validate(self):
         self.monotone_constraints = normalize_monotone(self.monotone_constraints)
+        self.interaction_constraints = normalize_interaction(self.interaction_constraints)
         if self.missing_policy not in self.MISSING_POLICIES:
             raise ValueError(f"missing_policy must be one of {self.MISSING_POLICIES}, got {self.missing_policy!r}")
         for name in ("subsample", "colsample_bytree", "colsample_bylevel", "colsample_bynode"):
@@ -337,6 +398,9 @@ class _Workspace:
         # weight bounds per heap node of a monotone fit (gbdt_split writes them level by level)
         self.blo = torch.full((nheap,), -np.inf, dtype=torch.float64, device=dev)
         self.bhi = torch.full((nheap,), np.inf, dtype=torch.float64, device=dev)
+        # split features of every heap node's ancestors, one bit each, of a fit with interaction
+        # constraints (uint32 words; gbdt_split writes them level by level)
+        self.path = torch.zeros(nheap, dtype=torch.int32, device=dev)
 
 
 # ---- per-round evaluation and early stopping -------------------------------------------------
@@ -680,7 +744,22 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
     The bounds live in two static workspace arrays (the hipGraph path replays them); sampling,
     weights, learned missing directions, evaluation, the row hole, data parallelism (the histograms
     are all-reduced before the scan) and checkpoints compose unchanged.  The length is checked
-    against the feature count here; all zero is the unconstrained fit, launch for launch."""
+    against the feature count here; all zero is the unconstrained fit, launch for launch.
+
+    Interaction constraints (``interaction_constraints`` of GBDTParams, xgboost's
+    FeatureInteractionConstraintHost; reference_gbdt's module docstring has the rules): a list of
+    groups of feature indices, which may overlap.  Every heap node carries ``path``, the set of
+    features its ancestors split on; with an empty path every feature is eligible, otherwise the
+    path's own features and every group that contains the whole path -- a feature in no group is only
+    followed by itself.  The split features are chosen on the device, so the split kernel carries the
+    path words down the heap itself (one static uint32 workspace array; the group masks travel in the
+    kernel arguments, so the hipGraph path replays them) and ANDs the allowed set into the word that
+    column sampling already gates candidates with: the sample is drawn first, then filtered, and a
+    node left with nothing does not split.  Only eligibility changes -- gain arithmetic, tie order and
+    acceptance are untouched, trees stay bitwise equal to the oracle's, and a constrained tree is an
+    ordinary tree for every walk, explainer and model file.  Indices are checked against the feature
+    count here; at most 32 groups; None, [] or only empty groups is the unconstrained fit, launch for
+    launch."""
     p = (params or GBDTParams()).validate()
     cuts_np, nbins = cuts
     d = int(len(nbins))
@@ -717,6 +796,8 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
     mono = p.monotone_signs(d)  # [d] signs or None
     mono_inc = 0 if mono is None else int(sum(1 << f for f in range(d) if mono[f] > 0))
     mono_dec = 0 if mono is None else int(sum(1 << f for f in range(d) if mono[f] < 0))
+    inter = p.interaction_masks(d)  # group masks or None
+    inter_named = None if inter is None else [list(g) for g in p.interaction_constraints]
     if learn and int(np.max(nbins, initial=0)) > MAX_BIN - 1:
         raise ValueError('missing_policy="learn": byte 255 is the missing slot, the cuts may hold at most 255 '
                          "real bins per feature (quantile_cuts(..., missing=True))")
@@ -734,8 +815,10 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
     # the policy is named only where it is not the default: a "last_bin" model serialises as before
     ens_kw = dict(depth=D, cuts=cuts_np, nbins=nbins, base_score=p.base_score,
                   params={**{k: v for k, v in p.__dict__.items()
-                             if k not in ("missing_policy", "monotone_constraints") or (k == "missing_policy" and learn)},
-                          "seed": seed, **({} if mono is None else {"monotone_constraints": [int(c) for c in mono]})})
+                             if k not in ("missing_policy", "monotone_constraints", "interaction_constraints")
+                             or (k == "missing_policy" and learn)},
+                          "seed": seed, **({} if mono is None else {"monotone_constraints": [int(c) for c in mono]}),
+                          **({} if inter is None else {"interaction_constraints": inter_named})})
     req = _eval_request(eval_set, eval_metric, early_stopping_rounds, hl, checkpoint,
                         comm is not None and comm.world_size > 1, T)
     ev = None
@@ -775,9 +858,12 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
         # they existed still resume
         dflt = p.SAMPLING_DEFAULTS
         sig_params = {k: v for k, v in p.__dict__.items()
-                      if k not in ("n_estimators", "monotone_constraints") and not (k in dflt and v == dflt[k])}
+                      if k not in ("n_estimators", "monotone_constraints", "interaction_constraints")
+                      and not (k in dflt and v == dflt[k])}
         if mono is not None:  # the resolved signs, whatever form they were given in
             sig_params["monotone_constraints"] = [int(c) for c in mono]
+        if inter is not None:  # the resolved groups
+            sig_params["interaction_constraints"] = inter_named
         # Which global rows the fit draws for is part of a sampled fit's configuration.  Every rank
         # must compute the SAME signature (rank 0 writes the checkpoint, all ranks load it), so
         # under data parallelism it names every rank's offset, not this rank's.
@@ -825,7 +911,7 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
                 q[~R.row_sample_mask(seed, t, keep + row_offset, p.subsample)] = 0
             tr, node = R.build_tree(b, q, cuts_np, nbins, D, p.reg_lambda, p.min_child_weight, p.gamma,
                                     p.learning_rate, gscale, hscale, comm, None if fmasks is None else fmasks[t],
-                                    learn, mono)
+                                    learn, mono, inter)
             feat[t], binv[t], thr[t], gain[t], leaf[t] = tr.feat, tr.bin, tr.thr, tr.gain, tr.leaf
             if learn:
                 dleft[t] = tr.default_left
@@ -918,6 +1004,8 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
         # monotone fit: the sign masks and the heap's weight bounds (static pointers)
         mono_arg = {} if mono is None else {"mono_inc": mono_inc, "mono_dec": mono_dec, "mono_lo": ptr(ws.blo),
                                             "mono_hi": ptr(ws.bhi)}
+        # interaction constraints: the group masks (constants) and the heap's path words (static pointer)
+        inter_arg = {} if inter is None else {"inter_groups": inter, "inter_path": ptr(ws.path)}
         for level in range(D):
             h0, nn = (1 << level) - 1, 1 << level
             if level == 0 and prev is not None:
@@ -931,7 +1019,7 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
                 comm.all_reduce_(ws.hist[h0 * HIST_ENTRIES:(h0 + nn) * HIST_ENTRIES])
             m.gbdt_split(ptr(ws.hist), ptr(ws.gcnt), level, d, ptr(nt), ptr(ct), ginv, hinv, lam, mcw, gam,
                          ptr(o_feat), ptr(o_bin), ptr(o_thr), ptr(o_gain), ptr(ws.ng), ptr(ws.nh), st, *fmask_arg,
-                         **miss_arg, **mono_arg)
+                         **miss_arg, **mono_arg, **inter_arg)
             if level == D - 1:
                 break  # leaves: the margin walk and gbdt_leaf (split-kernel child sums) need no partition
             if n_fit:

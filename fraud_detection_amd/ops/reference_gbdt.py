@@ -51,6 +51,21 @@ function here is what it was): cons[f] in {-1, 0, +1}, every heap node carries w
 * leaf = float32(eta * w(G, H)) under the leaf node's bounds.
 With ``missing`` the missing rows count in whichever side the candidate puts them.
 
+Interaction constraints (``interaction=`` group masks; default off, and off means every function
+here is what it was): a list of groups, each a set of feature indices in [0, d) given as a bit mask;
+groups may overlap and a feature may be in none -- xgboost's FeatureInteractionConstraintHost
+(Reset / SplitImpl / Query) as a pure function of the path:
+
+* a heap node's ``path`` is the set of split features of its proper ancestors that did split; a
+  pass-through ancestor adds nothing and hands its path unchanged to both children;
+* path empty (the root, or only pass-through ancestors): every one of the d features is allowed;
+* otherwise allowed = path | union of the groups g with path a subset of g (interaction_allowed): a
+  feature in no group may only be followed by itself, a feature in two groups opens both until a
+  later split narrows the path to one of them;
+* only eligibility changes: the node's candidates are those of ``fmask & allowed`` (the column
+  sample is drawn first, then filtered; nothing left means no split) -- gain arithmetic, validity
+  tests, tie order and the acceptance rule are untouched, and best_split is what it was.
+
 xgboost itself is not installed in this image, so parity with xgboost is "unpinned"; the
 semantics above follow xgboost's hist updater (train_model.py:69-80 uses XGBClassifier).
 """
@@ -329,13 +344,29 @@ def bins_go_right(v: np.ndarray, b, default_left) -> np.ndarray:
     return np.where((v == MISSING_BIN) & (np.asarray(default_left) != 0), False, v > b)
 
 
+def interaction_allowed(path_mask: int, groups, d: int) -> int:
+    """Allowed-feature bits of a node whose ancestors split on the features of ``path_mask``, under
+    the interaction groups ``groups`` (bit masks) of a d-feature fit: all d features for an empty
+    path, else the path's own features and every group that contains the whole path."""
+    path_mask = int(path_mask)
+    if path_mask == 0:
+        return (1 << d) - 1
+    allowed = path_mask
+    for g in groups:
+        if path_mask & ~int(g) == 0:
+            allowed |= int(g)
+    return allowed
+
+
 def build_tree(bins: np.ndarray, q: np.ndarray, cuts: np.ndarray, nbins: np.ndarray, depth: int, lam: float,
                mcw: float, gamma: float, eta: float, gscale: float, hscale: float, comm=None, fmasks=None,
-               missing: bool = False, monotone=None):
+               missing: bool = False, monotone=None, interaction=None):
     """Grow one depth-`depth` heap tree.  Returns (TreeArrays, leaf index per row [n]).
     ``fmasks``: uint32 [2^depth - 1] allowed-feature bits per heap node (feature_masks), or None.
     ``missing``: byte 255 of ``bins`` is the missing slot; TreeArrays.default_left is filled.
-    ``monotone``: [d] signs in {-1, 0, 1} (None: unconstrained); every node gets weight bounds."""
+    ``monotone``: [d] signs in {-1, 0, 1} (None: unconstrained); every node gets weight bounds.
+    ``interaction``: group masks (None: unconstrained); every node gets its ancestors' feature set
+    and only fmask & interaction_allowed(path) may be picked."""
     n = bins.shape[0]
     d = int(len(nbins))
     ginv, hinv = 1.0 / gscale, 1.0 / hscale
@@ -351,6 +382,7 @@ def build_tree(bins: np.ndarray, q: np.ndarray, cuts: np.ndarray, nbins: np.ndar
     if monotone is not None:
         monotone = np.asarray(monotone, np.int64)
         blo, bhi = np.full(2 * nl - 1, -np.inf), np.full(2 * nl - 1, np.inf)
+    path = None if interaction is None else np.zeros(2 * nl - 1, np.int64)
     node = np.zeros(n, np.int64)  # index within the level
     for level in range(depth):
         nn = 1 << level
@@ -364,6 +396,8 @@ def build_tree(bins: np.ndarray, q: np.ndarray, cuts: np.ndarray, nbins: np.ndar
         for k in range(nn):
             hid = h0 + k
             fm = None if fmasks is None else int(fmasks[hid])
+            if interaction is not None:
+                fm = ((1 << d) - 1 if fm is None else fm) & interaction_allowed(path[hid], interaction, d)
             mono = None if monotone is None else (monotone, blo[hid], bhi[hid])
             if missing:
                 g_, f, b, GLq, HLq, Gq, Hq, dl = best_split(Hl[k], nbins, ginv, hinv, lam, mcw, fm, True, mono)
@@ -384,6 +418,8 @@ def build_tree(bins: np.ndarray, q: np.ndarray, cuts: np.ndarray, nbins: np.ndar
             if monotone is not None:
                 blo[lc], bhi[lc], blo[rc], bhi[rc] = mono_children(
                     int(monotone[f]) if split else 0, blo[hid], bhi[hid], GLq, HLq, Gq, Hq, ginv, hinv, lam, mcw)
+            if interaction is not None:
+                path[lc] = path[rc] = path[hid] | ((1 << f) if split else 0)
         node = 2 * node + right.astype(np.int64)
     return TreeArrays(feat, binv, thr, gain, leaf_values(ng, nh, depth, ginv, hinv, lam, mcw, eta, blo, bhi),
                       dleft if missing else None), node

@@ -75,10 +75,34 @@ def parse_gbdt_monotone(spec: str | None, names) -> dict | None:
     return out
 
 
+def parse_gbdt_interaction(spec: str | None, names) -> list | None:
+    """``--gbdt-interaction "Amount,Time;V14,V17,V12"`` -> [[feature index, ...], ...]: groups
+    separated by ``;``, column names by ``,``, the names resolved against the table's feature
+    columns.  None / empty: no constraints.  An unknown name, a name repeated inside one group or an
+    empty group is a ValueError."""
+    if spec is None or not spec.strip():
+        return None
+    names = list(names)
+    out = []
+    for group in spec.split(";"):
+        idx = []
+        for name in group.split(","):
+            name = name.strip()
+            if not name:
+                raise ValueError(f"--gbdt-interaction: expected NAME,NAME;NAME,..., got {group.strip()!r}")
+            if name not in names:
+                raise ValueError(f"--gbdt-interaction: the table has no feature column {name!r}")
+            if names.index(name) in idx:
+                raise ValueError(f"--gbdt-interaction: {name!r} is named twice in one group")
+            idx.append(names.index(name))
+        out.append(idx)
+    return out
+
+
 def run(settings: Settings | None = None, model_type: str = "logistic", cv_folds: int = 5, model_dir: str = "models",
         verbose: bool = True, cfg: TrainConfig | None = None, comm=None, gbdt_eval_metric=None,
         gbdt_early_stopping: int | None = None, gbdt_subsample: float = 1.0, gbdt_colsample_bytree: float = 1.0,
-        gbdt_seed: int = 0, gbdt_monotone: str | None = None) -> dict:
+        gbdt_seed: int = 0, gbdt_monotone: str | None = None, gbdt_interaction: str | None = None) -> dict:
     """Single process, or data parallel when ``comm`` spans several ranks (torchrun: one rank per
     GPU).  Every rank reads the table and derives the same split; each fits on its strided shard
     with RCCL all-reduced statistics, so all ranks hold the same model; rank 0 writes artifacts.
@@ -93,7 +117,11 @@ def run(settings: Settings | None = None, model_type: str = "logistic", cv_folds
     ``gbdt_monotone``: "Amount=1,V14=-1" -- monotone constraints by column name (parse_gbdt_monotone),
     in every CV fold and in the final fit; standardisation divides by a positive scale, so a sign on
     the raw column is the same sign on the standardised one.  The chosen signs land in the summary
-    under "gbdt_monotone"."""
+    under "gbdt_monotone".
+
+    ``gbdt_interaction``: "Amount,Time;V14,V17,V12" -- interaction constraints by column name
+    (parse_gbdt_interaction), in every CV fold and in the final fit.  The groups land in the summary
+    under "gbdt_interaction", by name."""
     s = settings or Settings.load()
     comm = comm if (comm is not None and comm.world_size > 1) else None
     lead = comm is None or comm.rank == 0
@@ -144,11 +172,14 @@ def run(settings: Settings | None = None, model_type: str = "logistic", cv_folds
 
         gbdt_mono = parse_gbdt_monotone(gbdt_monotone, names)
         gbdt_params = GBDTParams(subsample=gbdt_subsample, colsample_bytree=gbdt_colsample_bytree,
-                                 seed=gbdt_seed, monotone_constraints=gbdt_mono).validate()
+                                 seed=gbdt_seed, monotone_constraints=gbdt_mono,
+                                 interaction_constraints=parse_gbdt_interaction(gbdt_interaction, names)).validate()
     elif (gbdt_subsample, gbdt_colsample_bytree, gbdt_seed) != (1.0, 1.0, 0):
         raise ValueError("--gbdt-subsample / --gbdt-colsample-bytree / --gbdt-seed need --model gbdt")
     elif gbdt_monotone:
         raise ValueError("--gbdt-monotone needs --model gbdt")
+    elif gbdt_interaction:
+        raise ValueError("--gbdt-interaction needs --model gbdt")
     cv_scores = []
     from dataclasses import asdict
 
@@ -265,6 +296,8 @@ def run(settings: Settings | None = None, model_type: str = "logistic", cv_folds
                                     "colsample_bytree": gbdt_params.colsample_bytree, "seed": gbdt_params.seed}
     if gbdt_params is not None and gbdt_params.monotone_constraints:
         summary["gbdt_monotone"] = {names[f]: c for f, c in sorted(gbdt_params.monotone_constraints.items()) if c}
+    if gbdt_params is not None and gbdt_params.interaction_constraints:
+        summary["gbdt_interaction"] = [[names[f] for f in g] for g in gbdt_params.interaction_constraints]
     try:
         summary["registered_version"] = _track(s, model_type, res, summary, paths, Xte, names, say)
     except Exception as e:  # noqa: BLE001 - tracking is best effort (reference train_model.py:165-166)
@@ -321,7 +354,9 @@ def _job_signature(s, model_type, cv_folds, split_mode, cfg: dict, shape, comm, 
                             **({"gbdt_sampling": [gbdt_params.subsample, gbdt_params.colsample_bytree, gbdt_params.seed]}
                                if gbdt_params is not None and gbdt_params.sampled else {}),
                             **({"gbdt_monotone": sorted(gbdt_params.monotone_constraints.items())}
-                               if gbdt_params is not None and gbdt_params.monotone_constraints else {}))
+                               if gbdt_params is not None and gbdt_params.monotone_constraints else {}),
+                            **({"gbdt_interaction": [list(g) for g in gbdt_params.interaction_constraints]}
+                               if gbdt_params is not None and gbdt_params.interaction_constraints else {}))
 
 
 def _cross_validate(model_type, cfg, folds, take, comm, mode: str, progress: _Progress | None = None,
@@ -415,6 +450,8 @@ def _track(s: Settings, model_type, res, summary, paths, Xte, names, say):
             mlf.log_param(f"gbdt_{k}", v)
         if summary.get("gbdt_monotone"):
             mlf.log_param("gbdt_monotone", ",".join(f"{k}={v}" for k, v in summary["gbdt_monotone"].items()))
+        if summary.get("gbdt_interaction"):
+            mlf.log_param("gbdt_interaction", ";".join(",".join(g) for g in summary["gbdt_interaction"]))
         ge = summary.get("gbdt_eval")
         if ge:
             mlf.log_param("gbdt_eval_metric", ",".join(ge["metrics"]))
@@ -473,6 +510,10 @@ def main(argv=None):
     ap.add_argument("--gbdt-monotone", default=None, metavar="NAME=SIGN,...",
                     help='monotone constraints by column name, e.g. "Amount=1,V14=-1": the score never falls (1) or '
                          "never rises (-1) as the column grows; an unknown name is an error")
+    ap.add_argument("--gbdt-interaction", default=None, metavar="NAME,NAME;NAME,...",
+                    help='interaction constraints by column name, e.g. "Amount,Time;V14,V17,V12": groups separated '
+                         "by ';'; below a path of split columns a node may use those columns and every group that "
+                         "contains them all; an unknown name is an error")
     a = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO)
     comm = None
@@ -491,7 +532,7 @@ def main(argv=None):
                   gbdt_eval_metric=a.gbdt_eval_metric.split(",") if a.gbdt_eval_metric else None,
                   gbdt_early_stopping=a.gbdt_early_stopping, gbdt_subsample=a.gbdt_subsample,
                   gbdt_colsample_bytree=a.gbdt_colsample_bytree, gbdt_seed=a.gbdt_seed,
-                  gbdt_monotone=a.gbdt_monotone)
+                  gbdt_monotone=a.gbdt_monotone, gbdt_interaction=a.gbdt_interaction)
     finally:
         if comm is not None:
             comm.close()

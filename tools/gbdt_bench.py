@@ -5,12 +5,16 @@ credit_card-shaped synthetic rows after SMOTE, plus test AUC and inference rate.
     python tools/gbdt_bench.py [--rows 10000000] [--trees 100] [--json out.json]
                                [--subsample 0.8] [--colsample-bytree 0.5] [--seed 0] [--weights]
                                [--monotone "1:-1,2:1,3:-1,4:1,29:1"]
+                               [--interaction "0,29;1,2,3,4,5;6,7,8"]
 
 --weights: every table row of the boosting call gets a sample weight (a time decay from 0.25 for the
 first row to 1.0 for the last, SMOTE's rows included), to measure what the weighted kernels cost on
 the same rows.  The pipeline itself takes no weights: the tool hands them to its ops/gbdt.fit call.
 --monotone: feature index : sign pairs (GBDTParams.monotone_constraints as a dict), to measure what
 the constrained split scan costs against the same fit without it.
+--interaction: groups of feature indices, ';' between groups and ',' between indices
+(GBDTParams.interaction_constraints), to measure what carrying the path words and filtering the
+eligible features costs against the same fit without it.
 """
 from __future__ import annotations
 
@@ -36,6 +40,7 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--weights", action="store_true")
     ap.add_argument("--monotone", default=None)
+    ap.add_argument("--interaction", default=None)
     a = ap.parse_args()
     from fraud_detection_amd.data.synthetic import separable
     from fraud_detection_amd.models.gbdt import GBDTPipeline
@@ -58,6 +63,9 @@ def main():
     mono = {int(k): int(v) for k, v in (item.split(":") for item in a.monotone.split(","))} if a.monotone else None
     if mono:
         sampling["monotone_constraints"] = mono
+    inter = [[int(f) for f in g.split(",")] for g in a.interaction.split(";")] if a.interaction else None
+    if inter:
+        sampling["interaction_constraints"] = inter
     pipe = GBDTPipeline(TrainConfig(), gb.GBDTParams(n_estimators=a.trees, max_depth=a.depth, **sampling))
     GBDTPipeline(TrainConfig(), gb.GBDTParams(n_estimators=2, max_depth=a.depth, **sampling)).fit(X, y)  # warm-up
     torch.cuda.synchronize()
@@ -81,9 +89,11 @@ def main():
            "auc": round(ev["auc"], 6), "predict_rows_per_s": round(n_test / pred_s, 1),
            "scale_pos_weight": round(res.scale_pos_weight, 3)}
     if pipe.params.sampled:
-        out.update({k: v for k, v in sampling.items() if k != "monotone_constraints"})
+        out.update({k: v for k, v in sampling.items() if k not in ("monotone_constraints", "interaction_constraints")})
     if mono:
         out["monotone"] = a.monotone
+    if inter:
+        out["interaction"] = a.interaction
     if a.weights:
         out["weights"] = "linspace(0.25, 1.0)"
     print(json.dumps(out))
