@@ -954,18 +954,19 @@ PYBIND11_MODULE(_fdx_native, m) {
   m.def("gbdt_split", [](u hist, u gcnt, int level, int d, u nbins, u cuts, double ginv, double hinv, double lam,
                          double mcw, double gamma, u feat, u bin, u thr, u gain, u ng, u nh, u s, u fmask,
                          bool missing, uint32_t mono_inc, uint32_t mono_dec, u mono_lo, u mono_hi,
-                         const std::vector<uint32_t>& inter_groups, u inter_path) {
+                         const std::vector<uint32_t>& inter_groups, u inter_path, double reg_alpha,
+                         double max_delta_step) {
     fdx::launch_gbdt_split(P<unsigned long long>(hist), P<const int64_t>(gcnt), level, d, P<const int>(nbins),
                            P<const float>(cuts), ginv, hinv, lam, mcw, gamma, P<int>(feat), P<int>(bin), P<float>(thr),
                            P<double>(gain), P<long long>(ng), P<long long>(nh), S(s), P<const uint32_t>(fmask),
                            missing, mono_inc, mono_dec, P<double>(mono_lo), P<double>(mono_hi), inter_groups,
-                           P<uint32_t>(inter_path));
+                           P<uint32_t>(inter_path), reg_alpha, max_delta_step);
   }, py::arg("hist"), py::arg("gcnt"), py::arg("level"), py::arg("d"), py::arg("nbins"), py::arg("cuts"),
      py::arg("ginv"), py::arg("hinv"), py::arg("lam"), py::arg("mcw"), py::arg("gamma"), py::arg("feat"),
      py::arg("bin"), py::arg("thr"), py::arg("gain"), py::arg("ng"), py::arg("nh"), py::arg("s"),
      py::arg("fmask") = 0, py::arg("missing") = false, py::arg("mono_inc") = 0, py::arg("mono_dec") = 0,
      py::arg("mono_lo") = 0, py::arg("mono_hi") = 0, py::arg("inter_groups") = std::vector<uint32_t>{},
-     py::arg("inter_path") = 0);
+     py::arg("inter_path") = 0, py::arg("reg_alpha") = 0.0, py::arg("max_delta_step") = 0.0);
   m.def("gbdt_transpose", [](u bins, int64_t n, int d, u binsT, int64_t ldt, u s) {
     fdx::launch_gbdt_transpose(P<const uint8_t>(bins), n, d, P<uint8_t>(binsT), ldt, S(s));
   });
@@ -986,11 +987,13 @@ PYBIND11_MODULE(_fdx_native, m) {
                                 n_global, S(s), P<int64_t>(node_r), n_nodes);
   });
   m.def("gbdt_leaf", [](u ng, u nh, int depth, double ginv, double hinv, double lam, double mcw, double eta, u leaf,
-                        u s, u mono_lo, u mono_hi) {
+                        u s, u mono_lo, u mono_hi, double reg_alpha, double max_delta_step) {
     fdx::launch_gbdt_leaf(P<const long long>(ng), P<const long long>(nh), depth, ginv, hinv, lam, mcw, eta,
-                          P<float>(leaf), S(s), P<const double>(mono_lo), P<const double>(mono_hi));
+                          P<float>(leaf), S(s), P<const double>(mono_lo), P<const double>(mono_hi), reg_alpha,
+                          max_delta_step);
   }, py::arg("ng"), py::arg("nh"), py::arg("depth"), py::arg("ginv"), py::arg("hinv"), py::arg("lam"),
-     py::arg("mcw"), py::arg("eta"), py::arg("leaf"), py::arg("s"), py::arg("mono_lo") = 0, py::arg("mono_hi") = 0);
+     py::arg("mcw"), py::arg("eta"), py::arg("leaf"), py::arg("s"), py::arg("mono_lo") = 0, py::arg("mono_hi") = 0,
+     py::arg("reg_alpha") = 0.0, py::arg("max_delta_step") = 0.0);
   m.def("gbdt_margin", [](u binsT, int64_t ldt, int64_t n, u feat, u bin, u leaf, int depth, u margin, u label,
                           float spw, float gscale, float hscale, u gh, u s) {
     fdx::launch_gbdt_margin(P<const uint8_t>(binsT), ldt, n, P<const int>(feat), P<const int>(bin),

@@ -781,6 +781,17 @@ struct SplitOut {
 // feature that is not allowed loses only its candidate, as under column subsampling.  The group
 // words travel by value in the kernel arguments, so the launcher checks them and a captured graph
 // replays them.  Without an InterArgs the kernel is the code and the arguments it was.
+//
+// REG (reg_alpha and max_delta_step; reference_gbdt's module docstring): a RegArgs in the pack MA,
+// after the MonoArgs and before the InterArgs.  With a = alpha and m = max_delta_step (0: off) a
+// side's weight is w = (H < mcw || H <= 0) ? 0 : -T(G) / (H + lambda), T(G) = G > a ? G - a :
+// (G < -a ? G + a : 0), then copysign(m, w) where m > 0 and fabs(w) > m, then the clamp into [lo, hi]
+// (-inf / +inf without MONO); its term is -(2 G w + (H + lambda) w w + 2 a fabs(w)), twice the
+// reduction of the regularised objective at w (T(G)^2 / (H + lambda) where nothing clamps).  Every
+// candidate, the node's own term and thread 0's recomputation of the winner's wl / wr take these in
+// place of mono_weight / mono_term; sign test, mid, validity, ties and acceptance are untouched.  The
+// two values travel by value, so the launcher checks them and a captured graph replays them.
+// Without a RegArgs the kernel is the code and the arguments it was.
 struct MonoArgs {
   uint32_t inc, dec;  // disjoint feature bits
   double* lo;         // [heap]
@@ -791,6 +802,9 @@ struct InterArgs {
   uint32_t n;                // groups in use
   uint32_t g[kGBMaxGroups];  // feature bits of each group
   uint32_t* path;            // [heap]
+};
+struct RegArgs {
+  double alpha, max_delta_step;  // both finite and >= 0; max_delta_step 0 = no cap
 };
 template <typename T, typename A0, typename... A>
 __host__ __device__ __forceinline__ T pack_get(A0 a0, A... a) {
@@ -808,6 +822,34 @@ __device__ __forceinline__ double mono_term(double G, double H, double lambda, d
   const double dn = H + lambda;
   return dn > 0.0 ? -(2.0 * G * w + dn * w * w) : 0.0;
 }
+__device__ __forceinline__ double reg_weight(double G, double H, double lambda, double mcw, double lo, double hi,
+                                             RegArgs r) {
+#pragma clang fp contract(off)
+  double w = 0.0;
+  if (!(H < mcw || H <= 0.0)) {
+    const double t = G > r.alpha ? G - r.alpha : (G < -r.alpha ? G + r.alpha : 0.0);
+    w = -t / (H + lambda);
+  }
+  if (r.max_delta_step > 0.0 && fabs(w) > r.max_delta_step) w = copysign(r.max_delta_step, w);
+  return w < lo ? lo : (w > hi ? hi : w);
+}
+__device__ __forceinline__ double reg_term(double G, double H, double lambda, double w, RegArgs r) {
+#pragma clang fp contract(off)
+  const double dn = H + lambda;
+  return dn > 0.0 ? -(2.0 * G * w + dn * w * w + 2.0 * r.alpha * fabs(w)) : 0.0;
+}
+// a side's weight under the node's bounds, and the term of a weight: with or without a RegArgs
+template <bool REG>
+__device__ __forceinline__ double side_weight(double G, double H, double lambda, double mcw, double lo, double hi,
+                                              RegArgs r) {
+  if constexpr (REG) return reg_weight(G, H, lambda, mcw, lo, hi, r);
+  else return mono_weight(G, H, lambda, mcw, lo, hi);
+}
+template <bool REG>
+__device__ __forceinline__ double side_term(double G, double H, double lambda, double w, RegArgs r) {
+  if constexpr (REG) return reg_term(G, H, lambda, w, r);
+  else return mono_term(G, H, lambda, w);
+}
 template <bool MISS, bool MONO = false, typename... MA>
 __global__ __launch_bounds__(kHistThreads) void gbdt_split_kernel(
     unsigned long long* __restrict__ hist, const int64_t* __restrict__ gcnt, int level, int d,
@@ -817,7 +859,9 @@ __global__ __launch_bounds__(kHistThreads) void gbdt_split_kernel(
     long long* __restrict__ ng, long long* __restrict__ nh, const uint32_t* __restrict__ fmask, MA... ma) {
 #pragma clang fp contract(off)
   constexpr bool INTER = (std::is_same_v<MA, InterArgs> || ...);
-  static_assert(sizeof...(MA) == (MONO ? 1 : 0) + (INTER ? 1 : 0), "tail: [MonoArgs with MONO] [InterArgs]");
+  constexpr bool REG = (std::is_same_v<MA, RegArgs> || ...);
+  static_assert(sizeof...(MA) == (MONO ? 1 : 0) + (REG ? 1 : 0) + (INTER ? 1 : 0),
+                "tail: [MonoArgs with MONO] [RegArgs] [InterArgs]");
   const int node = heap_first(level) + blockIdx.x;
   [[maybe_unused]] uint32_t inc = 0u, dec = 0u;
   [[maybe_unused]] double lo = -__builtin_inf(), hi = __builtin_inf();
@@ -827,6 +871,8 @@ __global__ __launch_bounds__(kHistThreads) void gbdt_split_kernel(
     inc = a.inc; dec = a.dec; blo = a.lo; bhi = a.hi;
     if (level != 0) { lo = blo[node]; hi = bhi[node]; }
   }
+  [[maybe_unused]] RegArgs reg{0.0, 0.0};
+  if constexpr (REG) reg = pack_get<RegArgs>(ma...);
   // column subsampling: bit f of fmask[node] = feature f may be picked (null: every feature).  A
   // masked-out feature loses only its candidate: its wave still stores a derived node's H = parent -
   // sibling (the children subtract from it) and feature 0's wave still publishes the node totals.
@@ -895,7 +941,8 @@ __global__ __launch_bounds__(kHistThreads) void gbdt_split_kernel(
     // zero-Hessian side: 0/0 or G^2/0 otherwise) -- the oracle's rule, reference_gbdt.py
     const double dn = Hs + lambda;
     double root;
-    if constexpr (MONO) root = mono_term(G, Hs, lambda, mono_weight(G, Hs, lambda, min_child_weight, lo, hi));
+    if constexpr (MONO || REG)
+      root = side_term<REG>(G, Hs, lambda, side_weight<REG>(G, Hs, lambda, min_child_weight, lo, hi, reg), reg);
     else root = dn > 0.0 ? G * G / dn : 0.0;
     [[maybe_unused]] const bool up = (inc >> f) & 1u, down = (dec >> f) & 1u;  // wave-uniform
     const int nb = nbins[f];
@@ -908,10 +955,10 @@ __global__ __launch_bounds__(kHistThreads) void gbdt_split_kernel(
       const double GL = (double)GLq * ginv, HL = (double)HLq * hinv;
       const double GR = (double)(Gq - GLq) * ginv, HR = (double)(Hq - HLq) * hinv;
       if (in_range && HL >= min_child_weight && HR >= min_child_weight) {
-        if constexpr (MONO) {
-          const double wl = mono_weight(GL, HL, lambda, min_child_weight, lo, hi);
-          const double wr = mono_weight(GR, HR, lambda, min_child_weight, lo, hi);
-          const double gain = (mono_term(GL, HL, lambda, wl) + mono_term(GR, HR, lambda, wr)) - root;
+        if constexpr (MONO || REG) {
+          const double wl = side_weight<REG>(GL, HL, lambda, min_child_weight, lo, hi, reg);
+          const double wr = side_weight<REG>(GR, HR, lambda, min_child_weight, lo, hi, reg);
+          const double gain = (side_term<REG>(GL, HL, lambda, wl, reg) + side_term<REG>(GR, HR, lambda, wr, reg)) - root;
           const bool ok = up ? wl <= wr : (down ? wl >= wr : true);
           if (ok && gain > best) { best = gain; bb = key; bgl = GLq; bhl = HLq; }
         } else {
@@ -987,9 +1034,10 @@ __global__ __launch_bounds__(kHistThreads) void gbdt_split_kernel(
       const bool up = split && ((inc >> bf) & 1u), down = split && ((dec >> bf) & 1u);
       if (up || down) {
         const long long GLq = fgl[bf], HLq = fhl[bf];
-        const double wl = mono_weight((double)GLq * ginv, (double)HLq * hinv, lambda, min_child_weight, lo, hi);
-        const double wr = mono_weight((double)(Gq - GLq) * ginv, (double)(Hq - HLq) * hinv, lambda,
-                                      min_child_weight, lo, hi);
+        const double wl = side_weight<REG>((double)GLq * ginv, (double)HLq * hinv, lambda, min_child_weight, lo, hi,
+                                           reg);
+        const double wr = side_weight<REG>((double)(Gq - GLq) * ginv, (double)(Hq - HLq) * hinv, lambda,
+                                           min_child_weight, lo, hi, reg);
         const double mid = (wl + wr) / 2.0;
         if (up) { lh = mid; rl = mid; } else { ll = mid; rh = mid; }
       }
@@ -1316,20 +1364,29 @@ __global__ __launch_bounds__(256) void gbdt_round_init_kernel(unsigned long long
 // leaf value is eta * weight.
 // blo / bhi (both or neither; null: no bounds): the heap's weight bounds of a monotone fit -- the
 // weight is clamped into its leaf node's [lo, hi] after the zero rule.
+// RA: empty, or one RegArgs (reg_alpha / max_delta_step by value): the weight is reg_weight's, soft
+// threshold and cap in front of the clamp.  Without it the kernel is the code and the arguments it was.
+template <typename... RA>
 __global__ void gbdt_leaf_kernel(const long long* __restrict__ ng, const long long* __restrict__ nh,
                                  int depth, double ginv, double hinv, double lambda,
                                  double min_child_weight, double eta, float* __restrict__ leaf,
-                                 const double* __restrict__ blo, const double* __restrict__ bhi) {
+                                 const double* __restrict__ blo, const double* __restrict__ bhi, RA... ra) {
 #pragma clang fp contract(off)
+  static_assert(sizeof...(RA) <= 1 && (std::is_same_v<RA, RegArgs> && ...), "tail: [RegArgs]");
   const int nl = 1 << depth;
   for (int i = threadIdx.x; i < nl; i += blockDim.x) {
     const int node = heap_first(depth) + i;
     const double G = (double)ng[node] * ginv, H = (double)nh[node] * hinv;
     double w = 0.0;
-    if (!(H < min_child_weight || H <= 0.0)) w = -G / (H + lambda);
-    if (blo != nullptr) {
-      const double lo = blo[node], hi = bhi[node];
-      w = w < lo ? lo : (w > hi ? hi : w);
+    if constexpr (sizeof...(RA) == 1) {
+      const double lo = blo != nullptr ? blo[node] : -__builtin_inf(), hi = blo != nullptr ? bhi[node] : __builtin_inf();
+      w = reg_weight(G, H, lambda, min_child_weight, lo, hi, ra...);
+    } else {
+      if (!(H < min_child_weight || H <= 0.0)) w = -G / (H + lambda);
+      if (blo != nullptr) {
+        const double lo = blo[node], hi = bhi[node];
+        w = w < lo ? lo : (w > hi ? hi : w);
+      }
     }
     leaf[i] = (float)(eta * w);
   }
@@ -1725,12 +1782,21 @@ void launch_gbdt_hist_l0_fused(const uint8_t* bins, uint32_t* gh, const int64_t*
   check_launch("gbdt_hist_reduce");
 }
 
+// reg_alpha / max_delta_step of gbdt_split and gbdt_leaf: finite and >= 0, refused before any launch
+static void check_reg_args(const char* who, double reg_alpha, double max_delta_step) {
+  if (!(reg_alpha >= 0.0) || !std::isfinite(reg_alpha))
+    throw std::runtime_error(std::string(who) + ": reg_alpha must be finite and >= 0");
+  if (!(max_delta_step >= 0.0) || !std::isfinite(max_delta_step))
+    throw std::runtime_error(std::string(who) + ": max_delta_step must be finite and >= 0");
+}
+
 void launch_gbdt_split(unsigned long long* hist, const int64_t* gcnt, int level, int d, const int* nbins,
                        const float* cuts, double ginv, double hinv, double lambda,
                        double min_child_weight, double gamma, int* feat, int* bin, float* thr,
                        double* gain, long long* ng, long long* nh, hipStream_t stream, const uint32_t* fmask,
                        bool missing, uint32_t mono_inc, uint32_t mono_dec, double* mono_lo, double* mono_hi,
-                       const std::vector<uint32_t>& inter_groups, uint32_t* inter_path) {
+                       const std::vector<uint32_t>& inter_groups, uint32_t* inter_path, double reg_alpha,
+                       double max_delta_step) {
   if (level < 0 || (1 << level) > kGBMaxNodes + 1) throw std::runtime_error("gbdt_split: level out of range");
   if (d < 1 || d > kGBMaxFeat) throw std::runtime_error("gbdt_split: bad feature count");
   if (mono_inc & mono_dec) throw std::runtime_error("gbdt_split: monotone masks overlap");
@@ -1746,19 +1812,30 @@ void launch_gbdt_split(unsigned long long* hist, const int64_t* gcnt, int level,
   }
   if (inter && inter_path == nullptr) throw std::runtime_error("gbdt_split: interaction groups need the path array");
   if (!inter && inter_path != nullptr) throw std::runtime_error("gbdt_split: a path array needs interaction groups");
+  check_reg_args("gbdt_split", reg_alpha, max_delta_step);
+  const bool reg = reg_alpha != 0.0 || max_delta_step != 0.0;
+  const RegArgs ra{reg_alpha, max_delta_step};
   const MonoArgs ma{mono_inc, mono_dec, mono_lo, mono_hi};
   InterArgs ia{};
   ia.n = (uint32_t)inter_groups.size();
   for (size_t i = 0; i < inter_groups.size(); ++i) ia.g[i] = inter_groups[i];
   ia.path = inter_path;
-  // <MISS, MONO> and the tail the instantiation takes: nothing, MonoArgs, InterArgs or both
+  // <MISS, MONO> and the tail the instantiation takes, in the pack's order: [MonoArgs] [RegArgs]
+  // [InterArgs], each there or not -- sixteen instantiations with MISS
+  static_assert(std::is_trivially_copyable_v<RegArgs> && sizeof(RegArgs) == 2 * sizeof(double),
+                "RegArgs travels by value in the kernel arguments");
   auto go = [&](auto miss, auto mn, auto... tail) {
     gbdt_split_kernel<decltype(miss)::value, decltype(mn)::value, decltype(tail)...>
         <<<1 << level, kHistThreads, 0, stream>>>(hist, gcnt, level, d, nbins, cuts, ginv, hinv, lambda,
                                                   min_child_weight, gamma, feat, bin, thr, gain, ng, nh, fmask, tail...);
   };
   auto by_tail = [&](auto miss) {
-    if (mono && inter) go(miss, std::true_type{}, ma, ia);
+    if (reg) {
+      if (mono && inter) go(miss, std::true_type{}, ma, ra, ia);
+      else if (mono) go(miss, std::true_type{}, ma, ra);
+      else if (inter) go(miss, std::false_type{}, ra, ia);
+      else go(miss, std::false_type{}, ra);
+    } else if (mono && inter) go(miss, std::true_type{}, ma, ia);
     else if (mono) go(miss, std::true_type{}, ma);
     else if (inter) go(miss, std::false_type{}, ia);
     else go(miss, std::false_type{});
@@ -1800,11 +1877,16 @@ void launch_gbdt_round_init(unsigned long long* hist, int64_t hist_words, int64_
 
 void launch_gbdt_leaf(const long long* ng, const long long* nh, int depth, double ginv, double hinv,
                       double lambda, double min_child_weight, double eta, float* leaf, hipStream_t stream,
-                      const double* mono_lo, const double* mono_hi) {
+                      const double* mono_lo, const double* mono_hi, double reg_alpha, double max_delta_step) {
   if ((mono_lo == nullptr) != (mono_hi == nullptr))
     throw std::runtime_error("gbdt_leaf: monotone bounds need both arrays or neither");
-  gbdt_leaf_kernel<<<1, 256, 0, stream>>>(ng, nh, depth, ginv, hinv, lambda, min_child_weight, eta, leaf, mono_lo,
-                                          mono_hi);
+  check_reg_args("gbdt_leaf", reg_alpha, max_delta_step);
+  if (reg_alpha != 0.0 || max_delta_step != 0.0)
+    gbdt_leaf_kernel<<<1, 256, 0, stream>>>(ng, nh, depth, ginv, hinv, lambda, min_child_weight, eta, leaf, mono_lo,
+                                            mono_hi, RegArgs{reg_alpha, max_delta_step});
+  else
+    gbdt_leaf_kernel<<<1, 256, 0, stream>>>(ng, nh, depth, ginv, hinv, lambda, min_child_weight, eta, leaf, mono_lo,
+                                            mono_hi);
   check_launch("gbdt_leaf");
 }
 

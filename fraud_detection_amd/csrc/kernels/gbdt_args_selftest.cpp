@@ -1,13 +1,15 @@
 // Host-side self-test of the GBDT launchers whose signatures grew for missing_policy="learn"
 // (gbdt.hip launch_gbdt_bin / launch_gbdt_split / launch_gbdt_predict, quantile.hip
 // launch_quantile_select), for monotone constraints (launch_gbdt_split / launch_gbdt_leaf) and for
-// interaction constraints (launch_gbdt_split): every argument check must throw BEFORE anything is
+// interaction constraints (launch_gbdt_split) and for reg_alpha / max_delta_step (launch_gbdt_split /
+// launch_gbdt_leaf): every argument check must throw BEFORE anything is
 // launched, whatever the new trailing arguments are, and the old call forms (trailing arguments
 // left out) must still compile.  Built with -fsanitize=address,undefined on the host side (tools/sanitize_host.sh); it
 // needs no GPU: a call that passes its checks either launches or reports the missing device as a
 // std::runtime_error from check_launch, and both count as "got past the checks".
 #include <cstdint>
 #include <cstdio>
+#include <limits>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -122,6 +124,45 @@ int main() {
       // the earlier checks still come first, whatever the groups are
       expect_refused("gbdt_split bad d with groups", "bad feature count", [&] { split(31, {0x3u}, nullptr); });
     }
+  // reg_alpha / max_delta_step (the last two arguments of launch_gbdt_split and launch_gbdt_leaf):
+  // host values, finite and >= 0, checked before any launch with every other tail there or not
+  {
+    const double nan = std::numeric_limits<double>::quiet_NaN(), inf = std::numeric_limits<double>::infinity();
+    for (bool missing : {false, true})
+      for (uint32_t inc : {0x0u, 0x1u})
+        for (bool groups : {false, true}) {
+          auto split = [&](int d, double alpha, double mds) {
+            fdx::launch_gbdt_split(hist.data(), gc.data(), 0, d, i32.data(), f32.data(), 1.0, 1.0, 1.0, 1.0, 0.0,
+                                   i32.data(), i32.data(), f32.data(), f64.data(), i64.data(), i64.data(), nullptr,
+                                   nullptr, missing, inc, 0u, f64.data(), f64.data(),
+                                   groups ? std::vector<uint32_t>{0x3u} : std::vector<uint32_t>{},
+                                   groups ? pathw.data() : nullptr, alpha, mds);
+          };
+          expect_refused("gbdt_split alpha < 0", "reg_alpha must be finite and >= 0", [&] { split(4, -1.0, 0.0); });
+          expect_refused("gbdt_split alpha NaN", "reg_alpha must be finite and >= 0", [&] { split(4, nan, 1.0); });
+          expect_refused("gbdt_split alpha inf", "reg_alpha must be finite and >= 0", [&] { split(4, inf, 0.0); });
+          expect_refused("gbdt_split mds < 0", "max_delta_step must be finite and >= 0", [&] { split(4, 0.0, -0.5); });
+          expect_refused("gbdt_split mds NaN", "max_delta_step must be finite and >= 0", [&] { split(4, 1.0, nan); });
+          expect_refused("gbdt_split mds inf", "max_delta_step must be finite and >= 0", [&] { split(4, 0.0, inf); });
+          // the earlier checks still come first, whatever the two values are
+          expect_refused("gbdt_split bad d with alpha", "bad feature count", [&] { split(31, -1.0, nan); });
+        }
+    for (double* b : {static_cast<double*>(nullptr), f64.data()}) {
+      auto leaf = [&](double alpha, double mds) {
+        fdx::launch_gbdt_leaf(i64.data(), i64.data(), 3, 1.0, 1.0, 1.0, 1.0, 0.1, f32.data(), nullptr, b, b, alpha, mds);
+      };
+      expect_refused("gbdt_leaf alpha < 0", "reg_alpha must be finite and >= 0", [&] { leaf(-1.0, 0.0); });
+      expect_refused("gbdt_leaf alpha NaN", "reg_alpha must be finite and >= 0", [&] { leaf(nan, 0.0); });
+      expect_refused("gbdt_leaf alpha inf", "reg_alpha must be finite and >= 0", [&] { leaf(inf, 0.0); });
+      expect_refused("gbdt_leaf mds < 0", "max_delta_step must be finite and >= 0", [&] { leaf(0.0, -1.0); });
+      expect_refused("gbdt_leaf mds NaN", "max_delta_step must be finite and >= 0", [&] { leaf(0.0, nan); });
+      expect_refused("gbdt_leaf mds inf", "max_delta_step must be finite and >= 0", [&] { leaf(1.0, inf); });
+    }
+    expect_refused("gbdt_leaf lo only with alpha", "both arrays or neither", [&] {
+      fdx::launch_gbdt_leaf(i64.data(), i64.data(), 3, 1.0, 1.0, 1.0, 1.0, 0.1, f32.data(), nullptr, f64.data(), nullptr,
+                            -1.0, 0.0);
+    });
+  }
   expect_refused("gbdt_leaf lo only", "both arrays or neither", [&] {
     fdx::launch_gbdt_leaf(i64.data(), i64.data(), 3, 1.0, 1.0, 1.0, 1.0, 0.1, f32.data(), nullptr, f64.data(), nullptr);
   });
@@ -170,6 +211,17 @@ int main() {
     fdx::launch_gbdt_split(hist.data(), gc.data(), -1, 4, i32.data(), f32.data(), 1.0, 1.0, 1.0, 1.0, 0.0, i32.data(),
                            i32.data(), f32.data(), f64.data(), i64.data(), i64.data(), nullptr);
   });
+  // ... and the forms that end at the monotone and at the interaction arguments
+  expect_refused("gbdt_split, monotone form", "level out of range", [&] {
+    fdx::launch_gbdt_split(hist.data(), gc.data(), -1, 4, i32.data(), f32.data(), 1.0, 1.0, 1.0, 1.0, 0.0, i32.data(),
+                           i32.data(), f32.data(), f64.data(), i64.data(), i64.data(), nullptr, nullptr, false, 0x1u, 0u,
+                           f64.data(), f64.data());
+  });
+  expect_refused("gbdt_split, interaction form", "level out of range", [&] {
+    fdx::launch_gbdt_split(hist.data(), gc.data(), -1, 4, i32.data(), f32.data(), 1.0, 1.0, 1.0, 1.0, 0.0, i32.data(),
+                           i32.data(), f32.data(), f64.data(), i64.data(), i64.data(), nullptr, nullptr, false, 0u, 0u,
+                           nullptr, nullptr, {0x3u}, pathw.data());
+  });
   expect_refused("gbdt_predict, old form", "depth must be in [1, 8]", [&] {
     fdx::launch_gbdt_predict(f32.data(), 1, 30, 30, i32.data(), f32.data(), f32.data(), 1, 0, 0.0f, f32.data(), nullptr);
   });
@@ -185,6 +237,17 @@ int main() {
     expect_checked("gbdt_leaf, old form", [&] {
       fdx::launch_gbdt_leaf(i64.data(), i64.data(), 3, 1.0, 1.0, 1.0, 1.0, 0.1, f32.data(), nullptr);
     });
+    // the monotone form and valid reg_alpha / max_delta_step (zero included): past the checks
+    expect_checked("gbdt_leaf, monotone form", [&] {
+      fdx::launch_gbdt_leaf(i64.data(), i64.data(), 3, 1.0, 1.0, 1.0, 1.0, 0.1, f32.data(), nullptr, f64.data(),
+                            f64.data());
+    });
+    for (double alpha : {0.0, 0.5})
+      for (double mds : {0.0, 2.0})
+        expect_checked("gbdt_leaf, valid alpha / mds", [&] {
+          fdx::launch_gbdt_leaf(i64.data(), i64.data(), 3, 1.0, 1.0, 1.0, 1.0, 0.1, f32.data(), nullptr, nullptr, nullptr,
+                                alpha, mds);
+        });
   }
   if (failures) {
     std::printf("gbdt_args_selftest: %d failure(s)\n", failures);

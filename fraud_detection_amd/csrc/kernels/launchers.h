@@ -479,7 +479,11 @@ void launch_gbdt_split(unsigned long long* hist, const int64_t* gcnt, int level,
                        // (host values; they travel in the kernel arguments) and, with any group, the
                        // heap's path words, uint32 [2^(D+1) - 1], read at `level` and written for the
                        // children (gbdt.hip)
-                       const std::vector<uint32_t>& inter_groups = {}, uint32_t* inter_path = nullptr);
+                       const std::vector<uint32_t>& inter_groups = {}, uint32_t* inter_path = nullptr,
+                       // L1 regularisation and the weight cap (xgboost's reg_alpha / max_delta_step):
+                       // finite and >= 0, by value in the kernel arguments; both 0 launches the
+                       // instantiations without them (gbdt.hip)
+                       double reg_alpha = 0.0, double max_delta_step = 0.0);
 // row-major [n][32] bins -> feature-major [d][ldt] (the partition's per-row feature reads)
 void launch_gbdt_transpose(const uint8_t* bins, int64_t n, int d, uint8_t* binsT, int64_t ldt, hipStream_t stream);
 void launch_gbdt_partition(const uint8_t* binsT, int64_t ldt, const int* ridx, const uint8_t* nid, int64_t n,
@@ -492,7 +496,9 @@ void launch_gbdt_round_init(unsigned long long* hist, int64_t hist_words, int64_
 void launch_gbdt_leaf(const long long* ng, const long long* nh, int depth, double ginv, double hinv,
                       double lambda, double min_child_weight, double eta, float* leaf, hipStream_t stream,
                       // a monotone fit's weight bounds (both or neither): the leaf weight is clamped
-                      const double* mono_lo = nullptr, const double* mono_hi = nullptr);
+                      const double* mono_lo = nullptr, const double* mono_hi = nullptr,
+                      // reg_alpha / max_delta_step as in launch_gbdt_split; both 0 is the old kernel
+                      double reg_alpha = 0.0, double max_delta_step = 0.0);
 void launch_gbdt_margin(const uint8_t* binsT, int64_t ldt, int64_t n, const int* feat, const int* bin,
                         const float* leaf, int depth, float* margin, const uint8_t* label, float spw, float gscale,
                         float hscale, uint32_t* gh, hipStream_t stream);

@@ -2,7 +2,8 @@
 
 * ``GBDTClassifier`` -- estimator with xgboost.XGBClassifier's parameter names
   (n_estimators, learning_rate, max_depth, reg_lambda, min_child_weight, gamma, max_bin,
-  scale_pos_weight, base_score, monotone_constraints, interaction_constraints) over numpy arrays or torch tensors; device kernels on a GPU
+  scale_pos_weight, base_score, monotone_constraints, interaction_constraints, reg_alpha,
+  max_delta_step) over numpy arrays or torch tensors; device kernels on a GPU
   tensor, the numpy oracle on CPU.  Models serialise to JSON (no pickle).
 * ``GBDTPipeline`` -- the reference's per-fold recipe on device: StandardScaler fit on the
   fold's rows -> SMOTE (MFMA k-NN + Philox interpolation, fp32 rows) -> boosting -> exact AUC.
@@ -49,7 +50,8 @@ class GBDTClassifier:
                  eval_metric=None, early_stopping_rounds: int | None = None, subsample: float = 1.0,
                  colsample_bytree: float = 1.0, colsample_bylevel: float = 1.0, colsample_bynode: float = 1.0,
                  seed: int | None = None, random_state: int | None = None, missing_policy: str = "last_bin",
-                 monotone_constraints=None, interaction_constraints=None, **_ignored):
+                 monotone_constraints=None, interaction_constraints=None, reg_alpha: float = 0.0,
+                 max_delta_step: float = 0.0, **_ignored):
         # xgboost-only knobs the reference passes (objective, n_jobs) are accepted and ignored: the
         # objective is binary:logistic.  eval_metric and early_stopping_rounds are constructor
         # arguments as in xgboost >= 1.6; they act only when fit() gets an eval_set (the reference's
@@ -66,6 +68,9 @@ class GBDTClassifier:
         # "[[0, 2], [1, 3, 4]]" (indices, not names); below a path of split features a node may then
         # use the path's own features and every group that contains the whole path
         # (ops/reference_gbdt's module docstring has the rule).
+        # reg_alpha / max_delta_step: xgboost's L1 regularisation of the leaf weights and its cap on
+        # |weight| (0 = off; the knob xgboost recommends for extremely imbalanced logistic fits), both
+        # finite and >= 0 (ops/gbdt.fit_binned has the rules).
         if seed is None:
             seed = 0 if random_state is None else random_state
         self.params = gb.GBDTParams(n_estimators=n_estimators, learning_rate=learning_rate, max_depth=max_depth,
@@ -75,7 +80,8 @@ class GBDTClassifier:
                                     colsample_bylevel=colsample_bylevel, colsample_bynode=colsample_bynode,
                                     seed=int(seed), missing_policy=missing_policy,
                                     monotone_constraints=gb.normalize_monotone(monotone_constraints),
-                                    interaction_constraints=gb.normalize_interaction(interaction_constraints))
+                                    interaction_constraints=gb.normalize_interaction(interaction_constraints),
+                                    reg_alpha=reg_alpha, max_delta_step=max_delta_step)
         self.device = device
         self.eval_metric = eval_metric
         self.early_stopping_rounds = early_stopping_rounds

@@ -138,13 +138,20 @@ class GBDTParams:
     # (reference_gbdt's module docstring has the rule).  A nested sequence of ints or the string
     # "[[0, 2], [1, 3, 4]]"; None or no non-empty group: unconstrained, launch for launch.
     interaction_constraints: tuple | list | str | None = None
+    # xgboost's reg_alpha (L1 on the leaf weights: the soft threshold of G in weight and gain) and
+    # max_delta_step (|weight| capped before the monotone clamp; 0 = no cap, the knob xgboost
+    # recommends for logistic loss on extremely imbalanced classes).  Both finite and >= 0; both 0:
+    # the fit without them, launch for launch (fit_binned has the rules).
+    reg_alpha: float = 0.0
+    max_delta_step: float = 0.0
 
     MISSING_POLICIES = ("last_bin", "learn")
     # fields a checkpoint signature names only off their defaults (older checkpoints resume): the
     # sampling fields and, added the same way, the missing policy
     SAMPLING_DEFAULTS = {"subsample": 1.0, "colsample_bytree": 1.0, "colsample_bylevel": 1.0,
                          "colsample_bynode": 1.0, "seed": 0, "missing_policy": "last_bin",
-                         "monotone_constraints": None, "interaction_constraints": None}
+                         "monotone_constraints": None, "interaction_constraints": None,
+                         "reg_alpha": 0.0, "max_delta_step": 0.0}
 
     @property
     def colsampled(self) -> bool:
@@ -157,6 +164,12 @@ class GBDTParams:
     @property
     def learn_missing(self) -> bool:
         return self.missing_policy == "learn"
+
+    @property
+    def reg(self):
+        """(reg_alpha, max_delta_step) as floats, or None when both are 0 (nothing changes)."""
+        a, m = float(self.reg_alpha), float(self.max_delta_step)
+        return (a, m) if (a != 0.0 or m != 0.0) else None
 
     def monotone_signs(self, d: int):
         """int64 [d] signs of a d-feature fit, or None when nothing is constrained."""
@@ -204,7 +217,7 @@ class GBDTParams:
             raise ValueError("base_score must be in (0, 1)")
         if self.n_estimators < 0 or self.learning_rate <= 0:
             raise ValueError("bad n_estimators / learning_rate")
-        for name in ("reg_lambda", "min_child_weight", "gamma"):
+        for name in ("reg_lambda", "min_child_weight", "gamma", "reg_alpha", "max_delta_step"):
             v = float(getattr(self, name))
             if not np.isfinite(v) or v < 0.0:
                 raise ValueError(f"{name} must be finite and >= 0")
@@ -759,7 +772,22 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
     acceptance are untouched, trees stay bitwise equal to the oracle's, and a constrained tree is an
     ordinary tree for every walk, explainer and model file.  Indices are checked against the feature
     count here; at most 32 groups; None, [] or only empty groups is the unconstrained fit, launch for
-    launch."""
+    launch.
+
+    L1 regularisation and the weight cap (``reg_alpha`` and ``max_delta_step`` of GBDTParams, xgboost's
+    names; reference_gbdt's module docstring has the rules): with a = reg_alpha a side's weight is
+    -T(G) / (H + lambda), T the soft threshold of G at a, capped to +-max_delta_step where that is
+    positive and only then clamped into the monotone bounds; a side's gain term is twice the
+    reduction of the regularised objective G w + (H + lambda) w^2 / 2 + a |w| at that weight, whatever
+    clamped it.  Only the split scan and the leaf weights change, both fp64 functions of the integer
+    histogram sums: the two values travel by value in the arguments of gbdt_split and gbdt_leaf (the
+    hipGraph path replays them), trees stay bitwise equal to the oracle's, every leaf satisfies
+    |leaf| <= float32(learning_rate * max_delta_step), and a = 2 n max(scale_pos_weight, 1) or more
+    leaves every tree empty.  The fused level-0 pass runs no scan and is unaffected; sampling, weights,
+    learned missing directions, monotone and interaction constraints, evaluation, the row hole, data
+    parallelism (the scan sees all-reduced histograms) and checkpoints compose unchanged.  Both 0 is
+    the fit without them, launch for launch; model files and checkpoint signatures name the two only
+    off their defaults."""
     p = (params or GBDTParams()).validate()
     cuts_np, nbins = cuts
     d = int(len(nbins))
@@ -798,6 +826,7 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
     mono_dec = 0 if mono is None else int(sum(1 << f for f in range(d) if mono[f] < 0))
     inter = p.interaction_masks(d)  # group masks or None
     inter_named = None if inter is None else [list(g) for g in p.interaction_constraints]
+    reg = p.reg  # (reg_alpha, max_delta_step) or None
     if learn and int(np.max(nbins, initial=0)) > MAX_BIN - 1:
         raise ValueError('missing_policy="learn": byte 255 is the missing slot, the cuts may hold at most 255 '
                          "real bins per feature (quantile_cuts(..., missing=True))")
@@ -815,8 +844,11 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
     # the policy is named only where it is not the default: a "last_bin" model serialises as before
     ens_kw = dict(depth=D, cuts=cuts_np, nbins=nbins, base_score=p.base_score,
                   params={**{k: v for k, v in p.__dict__.items()
-                             if k not in ("missing_policy", "monotone_constraints", "interaction_constraints")
+                             if k not in ("missing_policy", "monotone_constraints", "interaction_constraints",
+                                          "reg_alpha", "max_delta_step")
                              or (k == "missing_policy" and learn)},
+                          **({} if not float(p.reg_alpha) else {"reg_alpha": float(p.reg_alpha)}),
+                          **({} if not float(p.max_delta_step) else {"max_delta_step": float(p.max_delta_step)}),
                           "seed": seed, **({} if mono is None else {"monotone_constraints": [int(c) for c in mono]}),
                           **({} if inter is None else {"interaction_constraints": inter_named})})
     req = _eval_request(eval_set, eval_metric, early_stopping_rounds, hl, checkpoint,
@@ -911,7 +943,7 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
                 q[~R.row_sample_mask(seed, t, keep + row_offset, p.subsample)] = 0
             tr, node = R.build_tree(b, q, cuts_np, nbins, D, p.reg_lambda, p.min_child_weight, p.gamma,
                                     p.learning_rate, gscale, hscale, comm, None if fmasks is None else fmasks[t],
-                                    learn, mono, inter)
+                                    learn, mono, inter, reg)
             feat[t], binv[t], thr[t], gain[t], leaf[t] = tr.feat, tr.bin, tr.thr, tr.gain, tr.leaf
             if learn:
                 dleft[t] = tr.default_left
@@ -1006,6 +1038,8 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
                                             "mono_hi": ptr(ws.bhi)}
         # interaction constraints: the group masks (constants) and the heap's path words (static pointer)
         inter_arg = {} if inter is None else {"inter_groups": inter, "inter_path": ptr(ws.path)}
+        # reg_alpha / max_delta_step: two constants of the split scan and the leaf weights
+        reg_arg = {} if reg is None else {"reg_alpha": reg[0], "max_delta_step": reg[1]}
         for level in range(D):
             h0, nn = (1 << level) - 1, 1 << level
             if level == 0 and prev is not None:
@@ -1019,7 +1053,7 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
                 comm.all_reduce_(ws.hist[h0 * HIST_ENTRIES:(h0 + nn) * HIST_ENTRIES])
             m.gbdt_split(ptr(ws.hist), ptr(ws.gcnt), level, d, ptr(nt), ptr(ct), ginv, hinv, lam, mcw, gam,
                          ptr(o_feat), ptr(o_bin), ptr(o_thr), ptr(o_gain), ptr(ws.ng), ptr(ws.nh), st, *fmask_arg,
-                         **miss_arg, **mono_arg, **inter_arg)
+                         **miss_arg, **mono_arg, **inter_arg, **reg_arg)
             if level == D - 1:
                 break  # leaves: the margin walk and gbdt_leaf (split-kernel child sums) need no partition
             if n_fit:
@@ -1035,7 +1069,7 @@ def fit_binned(bins: torch.Tensor, y: torch.Tensor, cuts, params: GBDTParams | N
             if dist:
                 comm.all_reduce_(ws.gcnt[c0:c0 + 2 * nn])
         m.gbdt_leaf(ptr(ws.ng), ptr(ws.nh), D, ginv, hinv, lam, mcw, float(p.learning_rate), ptr(o_leaf), st,
-                    *((ptr(ws.blo), ptr(ws.bhi)) if mono is not None else ()))
+                    *((ptr(ws.blo), ptr(ws.bhi)) if mono is not None else ()), **reg_arg)
         if n and not defer_margin and grad_next and wt is not None and sub_on:
             m.gbdt_margin_sampled_weighted(ptr(binsT), ldt, n, ptr(o_feat), ptr(o_bin), ptr(o_leaf), D, ptr(margin),
                                            ptr(y), ptr(wt), spw, gscale, hscale, ptr(ws.gh), seed, t + 1, row_offset,

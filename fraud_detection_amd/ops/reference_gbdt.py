@@ -66,6 +66,30 @@ groups may overlap and a feature may be in none -- xgboost's FeatureInteractionC
   sample is drawn first, then filtered; nothing left means no split) -- gain arithmetic, validity
   tests, tie order and the acceptance rule are untouched, and best_split is what it was.
 
+L1 regularisation and max_delta_step (``reg=(alpha, max_delta_step)``; default None, and None means
+every function here is what it was): a = reg_alpha >= 0, m = max_delta_step >= 0 (0: off), [lo, hi]
+the node's monotone bounds ((-inf, +inf) when nothing is constrained).  Everything fp64, evaluated
+as written:
+
+* soft threshold T(G) = G > a ? G - a : (G < -a ? G + a : 0.0);
+* weight w = (H < mcw or H <= 0) ? 0 : -T(G) / (H + l); then, if m > 0 and fabs(w) > m,
+  w = copysign(m, w); last the monotone clamp w < lo ? lo : (w > hi ? hi : w) -- xgboost's order,
+  CalcWeight first, the evaluator's bounds after it;
+* term(G, H, w) = -(2 G w + (H + l) w w + 2 a fabs(w)) where H + l > 0, else 0: twice the reduction of
+  the regularised objective G w + (H + l) w^2 / 2 + a |w| at w; where nothing clamps it is
+  T(G)^2 / (H + l);
+* gain = (term(L, wl) + term(R, wr)) - term(node, w(node)), all three weights under the node's own
+  bounds.  With ``reg`` and no monotone constraint the scan takes this weight / term form with the
+  bounds -inf / +inf.  Validity tests, tie order, acceptance rule, the learned missing side, feature
+  masks, the monotone sign test and mid = (wl + wr) / 2 and the interaction paths are unchanged; wl,
+  wr and mid use the weight above;
+* leaf = float32(eta * w(G, H)) under the leaf node's bounds;
+* against xgboost: with only one of the two set and no monotone constraint these gains equal
+  xgboost's CalcGain in exact arithmetic (ThresholdL1(G)^2 / (H + l), resp. CalcGainGivenWeight).
+  With both set xgboost's CalcGain ADDS a |w| to the term, and under monotone constraints its
+  evaluator drops the a part of the term; here one formula, the objective's own, holds everywhere.
+  Not adopted either: a in the quantile cuts, any per-objective default of max_delta_step.
+
 xgboost itself is not installed in this image, so parity with xgboost is "unpinned"; the
 semantics above follow xgboost's hist updater (train_model.py:69-80 uses XGBClassifier).
 """
@@ -215,16 +239,18 @@ class TreeArrays:
 
 
 def best_split(H: np.ndarray, nbins: np.ndarray, ginv: float, hinv: float, lam: float, mcw: float,
-               fmask: int | None = None, missing: bool = False, mono=None):
+               fmask: int | None = None, missing: bool = False, mono=None, reg=None):
     """H: int64 [d, 256, 2] of one node.  Returns (gain, feature, bin, GLq, HLq, Gq, Hq).
     ``fmask``: bit f set = feature f may be picked (None: all).  The node totals come from feature
     0's sums whether or not feature 0 is allowed; with no valid allowed split the gain is -inf.
     ``missing``: slot 255 holds the missing rows' sums and the scan learns their side (module
     docstring); the return value gains default_left as its eighth element and bin may be -1.
     ``mono``: (cons [d] in {-1, 0, 1}, lo, hi) -- the node's weight bounds and the features' signs
-    (module docstring); None is the unconstrained scan, untouched."""
+    (module docstring); None is the unconstrained scan, untouched.
+    ``reg``: (alpha, max_delta_step) -- the weight / term form of the gain under L1 regularisation
+    and the weight cap (module docstring), with bounds -inf / +inf where ``mono`` is None."""
     if missing:
-        return _best_split_missing(H, nbins, ginv, hinv, lam, mcw, fmask, mono)
+        return _best_split_missing(H, nbins, ginv, hinv, lam, mcw, fmask, mono, reg)
     d = H.shape[0]
     cg = np.cumsum(H[:, :, 0], axis=1)
     chs = np.cumsum(H[:, :, 1], axis=1)
@@ -240,8 +266,8 @@ def best_split(H: np.ndarray, nbins: np.ndarray, ginv: float, hinv: float, lam: 
         gain = (np.where(dl > 0.0, GL * GL / dl, 0.0) + np.where(dr > 0.0, GR * GR / dr, 0.0)) - root
     b = np.arange(MAX_BIN)[None, :]
     valid = (b < (nbins[:d, None] - 1)) & (HL >= mcw) & (HR >= mcw)
-    if mono is not None:
-        gain, ok = _mono_gain(GL, HL, GR, HR, G, Hs, lam, mcw, mono)
+    if mono is not None or reg is not None:
+        gain, ok = _mono_gain(GL, HL, GR, HR, G, Hs, lam, mcw, mono, reg)
         valid &= ok
     if fmask is not None:
         valid &= ((int(fmask) >> np.arange(d)) & 1).astype(bool)[:, None]
@@ -251,56 +277,83 @@ def best_split(H: np.ndarray, nbins: np.ndarray, ginv: float, hinv: float, lam: 
     return float(gain[f, bb]), f, bb, int(cg[f, bb]), int(chs[f, bb]), Gq, Hq
 
 
-def mono_weight(G: float, H: float, lam: float, mcw: float, lo: float, hi: float) -> float:
-    """clamp(H < mcw or H <= 0 ? 0 : -G / (H + lam), lo, hi) on Python floats (IEEE fp64)."""
-    w = 0.0 if (H < mcw or H <= 0.0) else -G / (H + lam)
+def soft_threshold(G: float, alpha: float) -> float:
+    """T(G) = G > alpha ? G - alpha : (G < -alpha ? G + alpha : 0.0)."""
+    return G - alpha if G > alpha else (G + alpha if G < -alpha else 0.0)
+
+
+def mono_weight(G: float, H: float, lam: float, mcw: float, lo: float, hi: float, reg=None) -> float:
+    """clamp(H < mcw or H <= 0 ? 0 : -G / (H + lam), lo, hi) on Python floats (IEEE fp64).
+    ``reg`` = (alpha, m): -T(G) / (H + lam) instead, capped to copysign(m, w) where m > 0 and
+    fabs(w) > m, before the clamp."""
+    if reg is None:
+        w = 0.0 if (H < mcw or H <= 0.0) else -G / (H + lam)
+        return lo if w < lo else (hi if w > hi else w)
+    alpha, m = float(reg[0]), float(reg[1])
+    w = 0.0 if (H < mcw or H <= 0.0) else -soft_threshold(G, alpha) / (H + lam)
+    if m > 0.0 and abs(w) > m:
+        w = float(np.copysign(m, w))
     return lo if w < lo else (hi if w > hi else w)
 
 
-def mono_term(G: float, H: float, lam: float, w: float) -> float:
+def mono_term(G: float, H: float, lam: float, w: float, reg=None) -> float:
     dn = H + lam
-    return -(2.0 * G * w + dn * w * w) if dn > 0.0 else 0.0
+    if reg is None:
+        return -(2.0 * G * w + dn * w * w) if dn > 0.0 else 0.0
+    return -(2.0 * G * w + dn * w * w + 2.0 * float(reg[0]) * abs(w)) if dn > 0.0 else 0.0
 
 
-def _mono_weight_v(G, H, lam, mcw, lo, hi):
+def _mono_weight_v(G, H, lam, mcw, lo, hi, reg=None):
     with np.errstate(all="ignore"):
-        w = np.where((H < mcw) | (H <= 0.0), 0.0, -G / (H + lam))
+        if reg is None:
+            w = np.where((H < mcw) | (H <= 0.0), 0.0, -G / (H + lam))
+        else:
+            alpha, m = float(reg[0]), float(reg[1])
+            T = np.where(G > alpha, G - alpha, np.where(G < -alpha, G + alpha, 0.0))
+            w = np.where((H < mcw) | (H <= 0.0), 0.0, -T / (H + lam))
+            if m > 0.0:
+                w = np.where(np.abs(w) > m, np.copysign(m, w), w)
     return np.where(w < lo, lo, np.where(w > hi, hi, w))
 
 
-def _mono_term_v(G, H, lam, w):
+def _mono_term_v(G, H, lam, w, reg=None):
     dn = H + lam
     with np.errstate(all="ignore"):
-        return np.where(dn > 0.0, -(2.0 * G * w + dn * w * w), 0.0)
+        if reg is None:
+            return np.where(dn > 0.0, -(2.0 * G * w + dn * w * w), 0.0)
+        return np.where(dn > 0.0, -(2.0 * G * w + dn * w * w + 2.0 * float(reg[0]) * np.abs(w)), 0.0)
 
 
-def _mono_gain(GL, HL, GR, HR, G, Hs, lam, mcw, mono):
+def _mono_gain(GL, HL, GR, HR, G, Hs, lam, mcw, mono, reg=None):
     """(gain table, sign test) of candidates with fp64 side sums [d, K] under mono = (cons, lo, hi);
-    the expression order is gbdt.hip's (gbdt_split_kernel<MISS, true>)."""
+    the expression order is gbdt.hip's (gbdt_split_kernel<MISS, true>).  ``mono`` None (with ``reg``):
+    no signs, bounds -inf / +inf."""
+    if mono is None:
+        mono = (np.zeros(GL.shape[0], np.int64), -np.inf, np.inf)
     cons, lo, hi = mono
     lo, hi = float(lo), float(hi)
-    root = mono_term(G, Hs, lam, mono_weight(G, Hs, lam, mcw, lo, hi))
-    wl = _mono_weight_v(GL, HL, lam, mcw, lo, hi)
-    wr = _mono_weight_v(GR, HR, lam, mcw, lo, hi)
-    gain = (_mono_term_v(GL, HL, lam, wl) + _mono_term_v(GR, HR, lam, wr)) - root
+    root = mono_term(G, Hs, lam, mono_weight(G, Hs, lam, mcw, lo, hi, reg), reg)
+    wl = _mono_weight_v(GL, HL, lam, mcw, lo, hi, reg)
+    wr = _mono_weight_v(GR, HR, lam, mcw, lo, hi, reg)
+    gain = (_mono_term_v(GL, HL, lam, wl, reg) + _mono_term_v(GR, HR, lam, wr, reg)) - root
     c = np.asarray(cons, np.int64)[: GL.shape[0], None]
     return gain, np.where(c > 0, wl <= wr, np.where(c < 0, wl >= wr, True))
 
 
 def mono_children(c: int, lo: float, hi: float, GLq: int, HLq: int, Gq: int, Hq: int, ginv: float, hinv: float,
-                  lam: float, mcw: float):
+                  lam: float, mcw: float, reg=None):
     """(lo_left, hi_left, lo_right, hi_right) below a split on a feature of sign c whose left child
     has the sums (GLq, HLq): the weights are recomputed from the integers as the candidate's were."""
     lo, hi = float(lo), float(hi)
     if c == 0:
         return lo, hi, lo, hi
-    wl = mono_weight(float(GLq) * ginv, float(HLq) * hinv, lam, mcw, lo, hi)
-    wr = mono_weight(float(Gq - GLq) * ginv, float(Hq - HLq) * hinv, lam, mcw, lo, hi)
+    wl = mono_weight(float(GLq) * ginv, float(HLq) * hinv, lam, mcw, lo, hi, reg)
+    wr = mono_weight(float(Gq - GLq) * ginv, float(Hq - HLq) * hinv, lam, mcw, lo, hi, reg)
     mid = (wl + wr) / 2.0
     return (lo, mid, mid, hi) if c > 0 else (mid, hi, lo, mid)
 
 
-def _best_split_missing(H, nbins, ginv, hinv, lam, mcw, fmask, mono=None):
+def _best_split_missing(H, nbins, ginv, hinv, lam, mcw, fmask, mono=None, reg=None):
     """best_split with a learned side for slot 255.  Candidate (b, dl) sits at column 2 (b + 1) + dl
     of a [d, 512] gain table -- the tie order -- so one argmax picks the lowest feature, then the
     lowest b (-1 first), then default_left 0.  Column 0 (b = -1, nothing left) is no candidate."""
@@ -326,8 +379,8 @@ def _best_split_missing(H, nbins, ginv, hinv, lam, mcw, fmask, mono=None):
     b = (np.arange(2 * MAX_BIN) >> 1)[None, :] - 1
     valid = (b < (nbins[:d, None] - 1)) & (HL >= mcw) & (HR >= mcw)
     valid[:, 0] = False
-    if mono is not None:
-        gain, ok = _mono_gain(GL, HL, GR, HR, G, Hs, lam, mcw, mono)
+    if mono is not None or reg is not None:
+        gain, ok = _mono_gain(GL, HL, GR, HR, G, Hs, lam, mcw, mono, reg)
         valid &= ok
     if fmask is not None:
         valid &= ((int(fmask) >> np.arange(d)) & 1).astype(bool)[:, None]
@@ -360,13 +413,14 @@ def interaction_allowed(path_mask: int, groups, d: int) -> int:
 
 def build_tree(bins: np.ndarray, q: np.ndarray, cuts: np.ndarray, nbins: np.ndarray, depth: int, lam: float,
                mcw: float, gamma: float, eta: float, gscale: float, hscale: float, comm=None, fmasks=None,
-               missing: bool = False, monotone=None, interaction=None):
+               missing: bool = False, monotone=None, interaction=None, reg=None):
     """Grow one depth-`depth` heap tree.  Returns (TreeArrays, leaf index per row [n]).
     ``fmasks``: uint32 [2^depth - 1] allowed-feature bits per heap node (feature_masks), or None.
     ``missing``: byte 255 of ``bins`` is the missing slot; TreeArrays.default_left is filled.
     ``monotone``: [d] signs in {-1, 0, 1} (None: unconstrained); every node gets weight bounds.
     ``interaction``: group masks (None: unconstrained); every node gets its ancestors' feature set
-    and only fmask & interaction_allowed(path) may be picked."""
+    and only fmask & interaction_allowed(path) may be picked.
+    ``reg``: (alpha, max_delta_step) of the weights, gains and leaves (None: neither)."""
     n = bins.shape[0]
     d = int(len(nbins))
     ginv, hinv = 1.0 / gscale, 1.0 / hscale
@@ -400,9 +454,10 @@ def build_tree(bins: np.ndarray, q: np.ndarray, cuts: np.ndarray, nbins: np.ndar
                 fm = ((1 << d) - 1 if fm is None else fm) & interaction_allowed(path[hid], interaction, d)
             mono = None if monotone is None else (monotone, blo[hid], bhi[hid])
             if missing:
-                g_, f, b, GLq, HLq, Gq, Hq, dl = best_split(Hl[k], nbins, ginv, hinv, lam, mcw, fm, True, mono)
+                g_, f, b, GLq, HLq, Gq, Hq, dl = best_split(Hl[k], nbins, ginv, hinv, lam, mcw, fm, True, mono, reg)
             else:
-                (g_, f, b, GLq, HLq, Gq, Hq), dl = best_split(Hl[k], nbins, ginv, hinv, lam, mcw, fm, mono=mono), 0
+                (g_, f, b, GLq, HLq, Gq, Hq), dl = best_split(Hl[k], nbins, ginv, hinv, lam, mcw, fm, mono=mono,
+                                                                   reg=reg), 0
             if hid == 0:
                 ng[0], nh[0] = Gq, Hq
             split = accepts_split(g_, gamma)
@@ -417,11 +472,11 @@ def build_tree(bins: np.ndarray, q: np.ndarray, cuts: np.ndarray, nbins: np.ndar
                 ng[lc], nh[lc], ng[rc], nh[rc] = Gq, Hq, 0, 0
             if monotone is not None:
                 blo[lc], bhi[lc], blo[rc], bhi[rc] = mono_children(
-                    int(monotone[f]) if split else 0, blo[hid], bhi[hid], GLq, HLq, Gq, Hq, ginv, hinv, lam, mcw)
+                    int(monotone[f]) if split else 0, blo[hid], bhi[hid], GLq, HLq, Gq, Hq, ginv, hinv, lam, mcw, reg)
             if interaction is not None:
                 path[lc] = path[rc] = path[hid] | ((1 << f) if split else 0)
         node = 2 * node + right.astype(np.int64)
-    return TreeArrays(feat, binv, thr, gain, leaf_values(ng, nh, depth, ginv, hinv, lam, mcw, eta, blo, bhi),
+    return TreeArrays(feat, binv, thr, gain, leaf_values(ng, nh, depth, ginv, hinv, lam, mcw, eta, blo, bhi, reg),
                       dleft if missing else None), node
 
 
@@ -431,16 +486,21 @@ def accepts_split(gain: float, gamma: float) -> bool:
 
 
 def leaf_values(ng: np.ndarray, nh: np.ndarray, depth: int, ginv: float, hinv: float, lam: float, mcw: float,
-                eta: float, lo=None, hi=None) -> np.ndarray:
+                eta: float, lo=None, hi=None, reg=None) -> np.ndarray:
     """float32 [2^depth] leaf values from the heap's int64 node sums ng / nh (leaves at 2^depth - 1 ..).
-    ``lo`` / ``hi``: [heap] weight bounds of a monotone fit (the weight is clamped into them)."""
+    ``lo`` / ``hi``: [heap] weight bounds of a monotone fit (the weight is clamped into them).
+    ``reg``: (alpha, max_delta_step) -- the weight is mono_weight(..., reg)'s (module docstring)."""
     ni, nl = (1 << depth) - 1, 1 << depth
     leaf = np.zeros(nl, np.float32)
     for i in range(nl):
         G, H = float(ng[ni + i]) * ginv, float(nh[ni + i]) * hinv
-        w = 0.0 if (H < mcw or H <= 0.0) else -G / (H + lam)
-        if lo is not None:
-            w = float(lo[ni + i]) if w < lo[ni + i] else (float(hi[ni + i]) if w > hi[ni + i] else w)
+        if reg is not None:
+            w = mono_weight(G, H, lam, mcw, -np.inf if lo is None else float(lo[ni + i]),
+                            np.inf if hi is None else float(hi[ni + i]), reg)
+        else:
+            w = 0.0 if (H < mcw or H <= 0.0) else -G / (H + lam)
+            if lo is not None:
+                w = float(lo[ni + i]) if w < lo[ni + i] else (float(hi[ni + i]) if w > hi[ni + i] else w)
         leaf[i] = np.float32(eta * w)
     return leaf
 

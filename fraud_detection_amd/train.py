@@ -102,7 +102,8 @@ def parse_gbdt_interaction(spec: str | None, names) -> list | None:
 def run(settings: Settings | None = None, model_type: str = "logistic", cv_folds: int = 5, model_dir: str = "models",
         verbose: bool = True, cfg: TrainConfig | None = None, comm=None, gbdt_eval_metric=None,
         gbdt_early_stopping: int | None = None, gbdt_subsample: float = 1.0, gbdt_colsample_bytree: float = 1.0,
-        gbdt_seed: int = 0, gbdt_monotone: str | None = None, gbdt_interaction: str | None = None) -> dict:
+        gbdt_seed: int = 0, gbdt_monotone: str | None = None, gbdt_interaction: str | None = None,
+        gbdt_reg_alpha: float = 0.0, gbdt_max_delta_step: float = 0.0) -> dict:
     """Single process, or data parallel when ``comm`` spans several ranks (torchrun: one rank per
     GPU).  Every rank reads the table and derives the same split; each fits on its strided shard
     with RCCL all-reduced statistics, so all ranks hold the same model; rank 0 writes artifacts.
@@ -121,7 +122,11 @@ def run(settings: Settings | None = None, model_type: str = "logistic", cv_folds
 
     ``gbdt_interaction``: "Amount,Time;V14,V17,V12" -- interaction constraints by column name
     (parse_gbdt_interaction), in every CV fold and in the final fit.  The groups land in the summary
-    under "gbdt_interaction", by name."""
+    under "gbdt_interaction", by name.
+
+    ``gbdt_reg_alpha`` / ``gbdt_max_delta_step``: xgboost's L1 regularisation of the leaf weights and
+    its cap on |weight| (ops/gbdt.GBDTParams; both finite and >= 0, 0 = off), in every CV fold and in
+    the final fit.  Non-zero values land in the summary under "gbdt_reg"."""
     s = settings or Settings.load()
     comm = comm if (comm is not None and comm.world_size > 1) else None
     lead = comm is None or comm.rank == 0
@@ -173,13 +178,16 @@ def run(settings: Settings | None = None, model_type: str = "logistic", cv_folds
         gbdt_mono = parse_gbdt_monotone(gbdt_monotone, names)
         gbdt_params = GBDTParams(subsample=gbdt_subsample, colsample_bytree=gbdt_colsample_bytree,
                                  seed=gbdt_seed, monotone_constraints=gbdt_mono,
-                                 interaction_constraints=parse_gbdt_interaction(gbdt_interaction, names)).validate()
+                                 interaction_constraints=parse_gbdt_interaction(gbdt_interaction, names),
+                                 reg_alpha=gbdt_reg_alpha, max_delta_step=gbdt_max_delta_step).validate()
     elif (gbdt_subsample, gbdt_colsample_bytree, gbdt_seed) != (1.0, 1.0, 0):
         raise ValueError("--gbdt-subsample / --gbdt-colsample-bytree / --gbdt-seed need --model gbdt")
     elif gbdt_monotone:
         raise ValueError("--gbdt-monotone needs --model gbdt")
     elif gbdt_interaction:
         raise ValueError("--gbdt-interaction needs --model gbdt")
+    elif gbdt_reg_alpha or gbdt_max_delta_step:
+        raise ValueError("--gbdt-reg-alpha / --gbdt-max-delta-step need --model gbdt")
     cv_scores = []
     from dataclasses import asdict
 
@@ -298,6 +306,8 @@ def run(settings: Settings | None = None, model_type: str = "logistic", cv_folds
         summary["gbdt_monotone"] = {names[f]: c for f, c in sorted(gbdt_params.monotone_constraints.items()) if c}
     if gbdt_params is not None and gbdt_params.interaction_constraints:
         summary["gbdt_interaction"] = [[names[f] for f in g] for g in gbdt_params.interaction_constraints]
+    if gbdt_params is not None and gbdt_params.reg is not None:
+        summary["gbdt_reg"] = {"reg_alpha": gbdt_params.reg[0], "max_delta_step": gbdt_params.reg[1]}
     try:
         summary["registered_version"] = _track(s, model_type, res, summary, paths, Xte, names, say)
     except Exception as e:  # noqa: BLE001 - tracking is best effort (reference train_model.py:165-166)
@@ -356,7 +366,9 @@ def _job_signature(s, model_type, cv_folds, split_mode, cfg: dict, shape, comm, 
                             **({"gbdt_monotone": sorted(gbdt_params.monotone_constraints.items())}
                                if gbdt_params is not None and gbdt_params.monotone_constraints else {}),
                             **({"gbdt_interaction": [list(g) for g in gbdt_params.interaction_constraints]}
-                               if gbdt_params is not None and gbdt_params.interaction_constraints else {}))
+                               if gbdt_params is not None and gbdt_params.interaction_constraints else {}),
+                            **({"gbdt_reg": list(gbdt_params.reg)}
+                               if gbdt_params is not None and gbdt_params.reg is not None else {}))
 
 
 def _cross_validate(model_type, cfg, folds, take, comm, mode: str, progress: _Progress | None = None,
@@ -452,6 +464,8 @@ def _track(s: Settings, model_type, res, summary, paths, Xte, names, say):
             mlf.log_param("gbdt_monotone", ",".join(f"{k}={v}" for k, v in summary["gbdt_monotone"].items()))
         if summary.get("gbdt_interaction"):
             mlf.log_param("gbdt_interaction", ";".join(",".join(g) for g in summary["gbdt_interaction"]))
+        for k, v in (summary.get("gbdt_reg") or {}).items():
+            mlf.log_param(f"gbdt_{k}", v)
         ge = summary.get("gbdt_eval")
         if ge:
             mlf.log_param("gbdt_eval_metric", ",".join(ge["metrics"]))
@@ -514,6 +528,11 @@ def main(argv=None):
                     help='interaction constraints by column name, e.g. "Amount,Time;V14,V17,V12": groups separated '
                          "by ';'; below a path of split columns a node may use those columns and every group that "
                          "contains them all; an unknown name is an error")
+    ap.add_argument("--gbdt-reg-alpha", type=float, default=0.0,
+                    help="L1 regularisation of the leaf weights (xgboost's reg_alpha; 0: off)")
+    ap.add_argument("--gbdt-max-delta-step", type=float, default=0.0,
+                    help="cap on a leaf weight's magnitude before the learning rate (xgboost's max_delta_step, its "
+                         "advice for extremely imbalanced classes; 0: no cap)")
     a = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO)
     comm = None
@@ -532,7 +551,8 @@ def main(argv=None):
                   gbdt_eval_metric=a.gbdt_eval_metric.split(",") if a.gbdt_eval_metric else None,
                   gbdt_early_stopping=a.gbdt_early_stopping, gbdt_subsample=a.gbdt_subsample,
                   gbdt_colsample_bytree=a.gbdt_colsample_bytree, gbdt_seed=a.gbdt_seed,
-                  gbdt_monotone=a.gbdt_monotone, gbdt_interaction=a.gbdt_interaction)
+                  gbdt_monotone=a.gbdt_monotone, gbdt_interaction=a.gbdt_interaction,
+                  gbdt_reg_alpha=a.gbdt_reg_alpha, gbdt_max_delta_step=a.gbdt_max_delta_step)
     finally:
         if comm is not None:
             comm.close()

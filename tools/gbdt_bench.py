@@ -6,6 +6,7 @@ credit_card-shaped synthetic rows after SMOTE, plus test AUC and inference rate.
                                [--subsample 0.8] [--colsample-bytree 0.5] [--seed 0] [--weights]
                                [--monotone "1:-1,2:1,3:-1,4:1,29:1"]
                                [--interaction "0,29;1,2,3,4,5;6,7,8"]
+                               [--gbdt-reg-alpha 1.0] [--gbdt-max-delta-step 1.0]
 
 --weights: every table row of the boosting call gets a sample weight (a time decay from 0.25 for the
 first row to 1.0 for the last, SMOTE's rows included), to measure what the weighted kernels cost on
@@ -15,6 +16,8 @@ the constrained split scan costs against the same fit without it.
 --interaction: groups of feature indices, ';' between groups and ',' between indices
 (GBDTParams.interaction_constraints), to measure what carrying the path words and filtering the
 eligible features costs against the same fit without it.
+--gbdt-reg-alpha / --gbdt-max-delta-step: GBDTParams.reg_alpha / max_delta_step, to measure what the
+regularised weight / term form of the split scan costs against the same fit without it.
 """
 from __future__ import annotations
 
@@ -41,6 +44,8 @@ def main():
     ap.add_argument("--weights", action="store_true")
     ap.add_argument("--monotone", default=None)
     ap.add_argument("--interaction", default=None)
+    ap.add_argument("--gbdt-reg-alpha", type=float, default=0.0)
+    ap.add_argument("--gbdt-max-delta-step", type=float, default=0.0)
     a = ap.parse_args()
     from fraud_detection_amd.data.synthetic import separable
     from fraud_detection_amd.models.gbdt import GBDTPipeline
@@ -66,6 +71,8 @@ def main():
     inter = [[int(f) for f in g.split(",")] for g in a.interaction.split(";")] if a.interaction else None
     if inter:
         sampling["interaction_constraints"] = inter
+    if a.gbdt_reg_alpha or a.gbdt_max_delta_step:
+        sampling.update(reg_alpha=a.gbdt_reg_alpha, max_delta_step=a.gbdt_max_delta_step)
     pipe = GBDTPipeline(TrainConfig(), gb.GBDTParams(n_estimators=a.trees, max_depth=a.depth, **sampling))
     GBDTPipeline(TrainConfig(), gb.GBDTParams(n_estimators=2, max_depth=a.depth, **sampling)).fit(X, y)  # warm-up
     torch.cuda.synchronize()
@@ -89,7 +96,10 @@ def main():
            "auc": round(ev["auc"], 6), "predict_rows_per_s": round(n_test / pred_s, 1),
            "scale_pos_weight": round(res.scale_pos_weight, 3)}
     if pipe.params.sampled:
-        out.update({k: v for k, v in sampling.items() if k not in ("monotone_constraints", "interaction_constraints")})
+        out.update({k: v for k, v in sampling.items()
+                    if k not in ("monotone_constraints", "interaction_constraints", "reg_alpha", "max_delta_step")})
+    if pipe.params.reg is not None:
+        out.update(reg_alpha=a.gbdt_reg_alpha, max_delta_step=a.gbdt_max_delta_step)
     if mono:
         out["monotone"] = a.monotone
     if inter:

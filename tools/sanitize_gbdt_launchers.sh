@@ -1,7 +1,8 @@
 #!/usr/bin/env bash
 # Host-side sanitizer run of the GBDT launchers' argument checks (gbdt.hip launch_gbdt_bin /
 # launch_gbdt_split / launch_gbdt_leaf / launch_gbdt_predict, quantile.hip launch_quantile_select; old
-# and new call forms, the monotone masks and bounds and the interaction groups and path among them):
+# and new call forms, the monotone masks and bounds, the interaction groups and path and reg_alpha /
+# max_delta_step among them):
 # csrc/kernels/gbdt_args_selftest.cpp, a stand-alone program whose host code is built under
 # ASan + UBSan while the device code is built as usual.  Needs hipcc and no GPU; nothing sanitised is
 # loaded into Python.  Kept apart from sanitize_host.sh: it compiles gbdt.hip, a minute or two.
