@@ -863,6 +863,13 @@ PYBIND11_MODULE(_fdx_native, m) {
                            P<const float>(tmax), mc_pad, mc, self_off, k, P<int>(oidx), P<float>(oscore),
                            P<int>(lists), P<int>(counts), nsplit, S(s));
   });
+  m.def("knn3t_splits", [](int mq_pad, int mc_pad) { return fdx::knn3t_splits(mq_pad, mc_pad); });
+  m.def("knn_topk3t", [](u Q, u Qhl, int mq_pad, int mq, u C, u Chl, u tmax, int mc_pad, int mc, int64_t self_off,
+                         int k, u oidx, u oscore, u lists, u counts, u gmax, u thr, int nsplit, u s) {
+    fdx::launch_knn_topk3t(P<const float>(Q), P<const void>(Qhl), mq_pad, mq, P<const float>(C), P<const void>(Chl),
+                           P<const float>(tmax), mc_pad, mc, self_off, k, P<int>(oidx), P<float>(oscore),
+                           P<int>(lists), P<int>(counts), P<float>(gmax), P<float>(thr), nsplit, S(s));
+  });
   m.def("knn_topk", [](u Q, int mq_pad, int mq, u C, int mc_pad, int mc, int64_t self_off, int k, u oidx,
                        u oscore, u ws_score, u ws_idx, int nsplit, u s) {
     fdx::launch_knn_topk(P<const float>(Q), mq_pad, mq, P<const float>(C), mc_pad, mc,

@@ -1083,6 +1083,384 @@ __global__ __launch_bounds__(256) void knn_rerank_kernel(const float* __restrict
   }
 }
 
+// ---- bf16x3 two-pass collect: a threshold that is final from the first tile -------------------
+// knn_collect_kernel's per-tile cost is its RUNNING threshold (any-tests, LDS queue, flush with a
+// top-k insert per entry, seeds, compaction), and a streamed top-k appends ~k ln(n / k) candidates
+// per query whatever the tuning.  Here the 6-MFMA score runs twice and nothing else does:
+//   pass 1 (knn_groupmax_kernel): a lane pair (j, j + 32) holds a query's scores of the candidates
+//     c mod 32 = 4h + (r & 3) + 8 (r >> 2) in accumulator register r of half h -- 32 groups -- and
+//     keeps the running maximum of each (self masked, padding scores -3e38), plus the largest margin;
+//   knn_threshold_kernel: per query, v_K = the K-th largest of the 32 group maxima (elementwise max
+//     over the slices first), M = the largest margin of any slice, T = v_K - M.  The K groups' best
+//     candidates are K DISTINCT candidates with exact >= approx - m >= v_K - M = T, so the exact
+//     k-th best s_k >= T: knn_collect_kernel's argument with a threshold that never moves;
+//   pass 2 (knn_filter_kernel): appends (approx - m, index) when approx + m >= T.  Every candidate
+//     with exact >= s_k has approx + m >= exact >= T, so it is listed, in knn_collect_kernel's
+//     lists / counts layout with T in the threshold plane and M in the margin plane (a listed entry
+//     has lb = approx - m >= T - 2 m >= T - 2 M: knn_rerank_kernel's skip would keep it).
+//     A lane list past kListCap is counted, not stored: the re-rank's exact scan answers the query;
+//   knn_rerank_sparse_kernel: knn_rerank_kernel's exact re-score and ordering, 32 lanes per query.
+// gmax: [nsplit][qblocks][17][64] floats, rows 0..15 the lane's group maxima, row 16 its margin.
+__device__ __forceinline__ float knn_query_norm(const float* __restrict__ Q, int qg, int h) {
+  // 1.0001 ||q|| over the 30 feature columns (knn_collect_kernel's: half h sums columns 16h .. 16h + 15)
+  const float4* p = reinterpret_cast<const float4*>(Q + (int64_t)qg * kCols + 16 * h);
+  float s2 = 0.0f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const float4 v = p[k];
+    s2 = fmaf(v.x, v.x, s2);
+    s2 = fmaf(v.y, v.y, s2);
+    if (h == 0 || k < 3) {  // columns 30, 31 (query 1 / 0) are not features
+      s2 = fmaf(v.z, v.z, s2);
+      s2 = fmaf(v.w, v.w, s2);
+    }
+  }
+  s2 += __shfl_xor(s2, 32, kWave);
+  return sqrtf(s2) * 1.0001f;
+}
+
+// max(a, b) of two non-NaN floats as one v_med3_f32(a, b, +inf): fmaxf costs a canonicalizing
+// v_max_f32 x, x on every operand the compiler cannot prove quiet -- an MFMA result, a loop-carried
+// maximum -- which tripled the passes' VALU count per tile
+__device__ __forceinline__ float knn_max(float a, float b) { return __builtin_amdgcn_fmed3f(a, b, __builtin_inff()); }
+
+// The tile loop both passes share.  A wave scores every candidate tile against TWO query blocks
+// (2 x and 2 x + 1): the tile's 4 KiB of operands, fetched once, feed both 6-MFMA chains, which are
+// interleaved as knn_collect_kernel interleaves two tiles' (independent accumulators; per block
+// bitwise its sums).  That halves the bytes a pass pulls through L2 (740 MB at 13.6k x 13.6k with one
+// block per wave); on its own it measured neutral, the unconditional prefetch and knn_max above
+// gave the passes their last 10 % (profiles/pr4_knn_twopass).  Two tiles are in flight;
+// use(t, acc of block 0, acc of block 1, tmax[t]).
+struct KnnQFrag {
+  bf16x8_t h0, h1, l0, l1;
+};
+
+__device__ __forceinline__ KnnQFrag knn_load_qfrag(const uint4* __restrict__ Qhl, int qg, int h) {
+  const uint4* qr = Qhl + (int64_t)qg * 8;
+  return {__builtin_bit_cast(bf16x8_t, qr[h]), __builtin_bit_cast(bf16x8_t, qr[2 + h]),
+          __builtin_bit_cast(bf16x8_t, qr[4 + h]), __builtin_bit_cast(bf16x8_t, qr[6 + h])};
+}
+
+template <typename F>
+__device__ __forceinline__ void knn_stream_tiles(const KnnQFrag& qa, const KnnQFrag& qb,
+                                                 const uint4* __restrict__ Chl, const float* __restrict__ tmax,
+                                                 int lane, int t_lo, int t_hi, F&& use) {
+  auto fetch = [&](int t, uint4 (&a)[4], float& tmv) {
+    const uint4* p = Chl + (int64_t)t * 256 + lane;
+    a[0] = p[0]; a[1] = p[64]; a[2] = p[128]; a[3] = p[192];
+    tmv = tmax[t];
+  };
+  auto score = [&](const uint4 (&c)[4], f32x16_t& acc0, f32x16_t& acc1) {
+    const bf16x8_t ch0 = __builtin_bit_cast(bf16x8_t, c[0]), ch1 = __builtin_bit_cast(bf16x8_t, c[1]);
+    const bf16x8_t cl0 = __builtin_bit_cast(bf16x8_t, c[2]), cl1 = __builtin_bit_cast(bf16x8_t, c[3]);
+    acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cl0, qa.h0, acc0, 0, 0, 0);
+    acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cl0, qb.h0, acc1, 0, 0, 0);
+    acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cl1, qa.h1, acc0, 0, 0, 0);
+    acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cl1, qb.h1, acc1, 0, 0, 0);
+    acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ch0, qa.l0, acc0, 0, 0, 0);
+    acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ch0, qb.l0, acc1, 0, 0, 0);
+    acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ch1, qa.l1, acc0, 0, 0, 0);
+    acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ch1, qb.l1, acc1, 0, 0, 0);
+    acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ch0, qa.h0, acc0, 0, 0, 0);
+    acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ch0, qb.h0, acc1, 0, 0, 0);
+    acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ch1, qa.h1, acc0, 0, 0, 0);
+    acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ch1, qb.h1, acc1, 0, 0, 0);
+  };
+  if (t_lo >= t_hi) return;  // a slice with no tile
+  // Every prefetch is issued unconditionally, past the end clamped to the slice's last tile (fetched
+  // again, never used): with the loads behind a branch the compiler cannot count them and waits for
+  // ALL outstanding loads, the just-issued prefetch included, in front of every tile.
+  const int last = t_hi - 1;
+  uint4 ca[4], cb[4];
+  float tma, tmb;
+  fetch(t_lo, ca, tma);
+  fetch(t_lo + 1 < t_hi ? t_lo + 1 : last, cb, tmb);
+  for (int t = t_lo; t < t_hi; t += 2) {
+    {
+      f32x16_t acc0 = {}, acc1 = {};
+      score(ca, acc0, acc1);
+      const float tm = tma;
+      fetch(t + 2 < t_hi ? t + 2 : last, ca, tma);
+      use(t, acc0, acc1, tm);
+    }
+    {
+      f32x16_t acc0 = {}, acc1 = {};
+      score(cb, acc0, acc1);
+      const float tm = tmb;
+      fetch(t + 3 < t_hi ? t + 3 : last, cb, tmb);
+      if (t + 1 < t_hi) use(t + 1, acc0, acc1, tm);  // wave-uniform
+    }
+  }
+}
+
+// grid ((qblocks + 1) / 2, nsplit); an odd last block is scored twice and written once
+__global__ __launch_bounds__(kWave) void knn_groupmax_kernel(const float* __restrict__ Q,
+                                                             const uint4* __restrict__ Qhl,
+                                                             const uint4* __restrict__ Chl,
+                                                             const float* __restrict__ tmax, int qblocks, int mc_pad,
+                                                             int64_t self_offset, float* __restrict__ gmax) {
+  const int lane = threadIdx.x;
+  const int h = lane >> 5, j = lane & 31;
+  const int b0 = 2 * blockIdx.x;
+  const bool has1 = b0 + 1 < qblocks;  // wave-uniform
+  const int b1 = has1 ? b0 + 1 : b0;
+  const float qn0 = knn_query_norm(Q, b0 * 32 + j, h), qn1 = knn_query_norm(Q, b1 * 32 + j, h);
+  const KnnQFrag qa = knn_load_qfrag(Qhl, b0 * 32 + j, h), qb = knn_load_qfrag(Qhl, b1 * 32 + j, h);
+  // block b's self candidates self_offset + 32 b .. + 31 lie in tile ts + (b - b0) and, when
+  // self_offset is no multiple of 32, the tile after it; sr = the lane's self row relative to that tile
+  const int ts = self_offset >= 0 ? (int)((self_offset + b0 * 32) >> 5) : -4;
+  const int sr = self_offset >= 0 ? (int)((self_offset + b0 * 32) & 31) + j : -64;
+  const int d1 = b1 - b0;
+  float m0[16], m1[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) m0[r] = m1[r] = kNegBig;
+  float tmm = 0.0f;  // the margin grows with the tile's norm bound: the largest bound gives the largest margin
+  const int all_tiles = mc_pad / 32;
+  const int t_lo = (int)(((int64_t)all_tiles * blockIdx.y) / gridDim.y);
+  const int t_hi = (int)(((int64_t)all_tiles * (blockIdx.y + 1)) / gridDim.y);
+  auto take = [&](float (&m)[16], const f32x16_t& acc, int dt) {  // dt = t - the block's first self tile
+    if (dt == 0 || dt == 1) {  // wave-uniform: the self candidate stays out of the maxima
+      const int rs = sr - 32 * dt;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) m[r] = knn_max(m[r], 4 * h + (r & 3) + 8 * (r >> 2) == rs ? kNegBig : acc[r]);
+    } else {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) m[r] = knn_max(m[r], acc[r]);
+    }
+  };
+  knn_stream_tiles(qa, qb, Chl, tmax, lane, t_lo, t_hi,
+                   [&](int t, const f32x16_t& acc0, const f32x16_t& acc1, float tm) {
+                     tmm = fmaxf(tmm, tm);
+                     take(m0, acc0, t - ts);
+                     take(m1, acc1, t - ts - d1);
+                   });
+  float* o0 = gmax + (int64_t)(blockIdx.y * qblocks + b0) * 17 * kWave + lane;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) o0[r * kWave] = m0[r];
+  o0[16 * kWave] = kMarginScale * fmaf(qn0, tmm, 0.5f * tmm * tmm);
+  if (has1) {
+    float* o1 = o0 + 17 * kWave;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o1[r * kWave] = m1[r];
+    o1[16 * kWave] = kMarginScale * fmaf(qn1, tmm, 0.5f * tmm * tmm);
+  }
+}
+
+// One wave per query block, the lanes as in the passes: thr[q] = T, thr[mq_pad + q] = M.
+template <int K>
+__global__ __launch_bounds__(kWave) void knn_threshold_kernel(const float* __restrict__ gmax, int nsplit, int mq,
+                                                              float* __restrict__ thr) {
+  const int lane = threadIdx.x;
+  const int qg = blockIdx.x * 32 + (lane & 31);
+  float v[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) v[r] = kNegBig;
+  float M = 0.0f;
+  for (int s = 0; s < nsplit; ++s) {
+    const float* g = gmax + (int64_t)(s * gridDim.x + blockIdx.x) * 17 * kWave + lane;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) v[r] = fmaxf(v[r], g[r * kWave]);
+    M = fmaxf(M, g[16 * kWave]);
+  }
+  float bs[K];  // this half's K largest group maxima, descending
+#pragma unroll
+  for (int k = 0; k < K; ++k) bs[k] = kNegBig;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    float x = v[r];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const float hi = fmaxf(bs[k], x);
+      x = fminf(bs[k], x);
+      bs[k] = hi;
+    }
+  }
+  // the K-th largest of the union with the partner's (other half's) K largest
+  float ps[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) ps[k] = __shfl_xor(bs[k], 32, kWave);
+  int ia = 0, ib = 0;
+  float kth = kNegBig;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    float a = kNegBig, b = kNegBig;
+#pragma unroll
+    for (int u = 0; u < K; ++u) { if (u == ia) a = bs[u]; if (u == ib) b = ps[u]; }
+    const bool ta = a >= b;
+    kth = ta ? a : b;
+    ia += ta ? 1 : 0;
+    ib += ta ? 0 : 1;
+  }
+  if (lane < 32) {
+    thr[qg] = qg < mq ? kth - M : __builtin_inff();  // a padding query lists nothing
+    thr[(int64_t)gridDim.x * 32 + qg] = M;
+  }
+}
+
+// grid ((qblocks + 1) / 2, nsplit), as pass 1
+__global__ __launch_bounds__(kWave) void knn_filter_kernel(const float* __restrict__ Q, const uint4* __restrict__ Qhl,
+                                                           const uint4* __restrict__ Chl,
+                                                           const float* __restrict__ tmax,
+                                                           const float* __restrict__ thr, int qblocks, int mc_pad,
+                                                           int mc, int64_t self_offset, int2* __restrict__ lists,
+                                                           int* __restrict__ counts) {
+  const int lane = threadIdx.x;
+  const int h = lane >> 5, j = lane & 31;
+  const int b0 = 2 * blockIdx.x;
+  const bool has1 = b0 + 1 < qblocks;  // wave-uniform
+  const int b1 = has1 ? b0 + 1 : b0;
+  const int qg0 = b0 * 32 + j, qg1 = b1 * 32 + j;
+  const int64_t self0 = self_offset >= 0 ? self_offset + qg0 : -1, self1 = self_offset >= 0 ? self_offset + qg1 : -1;
+  const float qn0 = knn_query_norm(Q, qg0, h), qn1 = knn_query_norm(Q, qg1, h);
+  const KnnQFrag qa = knn_load_qfrag(Qhl, qg0, h), qb = knn_load_qfrag(Qhl, qg1, h);
+  const int64_t mq_pad = (int64_t)qblocks * 32;
+  const float T0 = thr[qg0], M0 = thr[mq_pad + qg0];
+  const float T1 = has1 ? thr[qg1] : __builtin_inff(), M1 = thr[mq_pad + qg1];  // the duplicate block lists nothing
+  int cnt0 = 0, cnt1 = 0;
+  const int64_t lbase0 = (int64_t)(blockIdx.y * qblocks + b0) * kListCap * kWave + lane;
+  const int64_t lbase1 = lbase0 + (int64_t)kListCap * kWave;
+  const int all_tiles = mc_pad / 32;
+  const int t_lo = (int)(((int64_t)all_tiles * blockIdx.y) / gridDim.y);
+  const int t_hi = (int)(((int64_t)all_tiles * (blockIdx.y + 1)) / gridDim.y);
+  auto filter = [&](int t, const f32x16_t& acc, float tm, float qn, float T, int64_t self_c, int64_t lbase, int& cnt) {
+    const float mg = kMarginScale * fmaf(qn, tm, 0.5f * tm * tm);
+    const float cut = T - mg;  // upper bound approx + mg >= T
+    float m4[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      m4[q] = knn_max(knn_max(acc[4 * q], acc[4 * q + 1]), knn_max(acc[4 * q + 2], acc[4 * q + 3]));
+    const float mx = knn_max(knn_max(m4[0], m4[1]), knn_max(m4[2], m4[3]));
+    if (!__any(mx >= cut)) return;
+    const int cbase = t * 32 + 4 * h;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      if (!__any(m4[q] >= cut)) continue;
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) {
+        const int ci = cbase + rr + 8 * q;
+        if (acc[4 * q + rr] >= cut && ci != self_c && ci < mc) {
+          if (cnt < kListCap) lists[lbase + (int64_t)cnt * kWave] = make_int2(__float_as_int(acc[4 * q + rr] - mg), ci);
+          ++cnt;  // past the cap: counted only (the re-rank scans this query exactly)
+        }
+      }
+    }
+  };
+  knn_stream_tiles(qa, qb, Chl, tmax, lane, t_lo, t_hi,
+                   [&](int t, const f32x16_t& acc0, const f32x16_t& acc1, float tm) {
+                     filter(t, acc0, tm, qn0, T0, self0, lbase0, cnt0);
+                     filter(t, acc1, tm, qn1, T1, self1, lbase1, cnt1);
+                   });
+  const int64_t ci0 = (int64_t)(blockIdx.y * qblocks + b0) * kWave + lane;
+  const int64_t plane = (int64_t)qblocks * gridDim.y * kWave;
+  counts[ci0] = cnt0;
+  counts[plane + ci0] = __float_as_int(T0);
+  counts[2 * plane + ci0] = __float_as_int(M0);
+  if (has1) {
+    counts[ci0 + kWave] = cnt1;
+    counts[plane + ci0 + kWave] = __float_as_int(T1);
+    counts[2 * plane + ci0 + kWave] = __float_as_int(M1);
+  }
+}
+
+// The re-rank for the two-pass lists: the same exact re-score and ordering as knn_rerank_kernel, so
+// the same result bit for bit, but 32 lanes per query, lane l taking the lane lists l, l + 32, ..
+// of the query's 2 nsplit (slice, half) lists.  The fixed threshold leaves ~5.6 entries per query
+// spread over 18-28 lists, nearly all empty: knn_rerank_kernel's 8 lanes read the lists' counts one
+// after the other, a chain of dependent loads that kept it at 41 us whatever the lists held
+// (profiles/pr4_knn_twopass).  No skip test: every listed entry has an upper bound >= T.
+template <int K>
+__global__ __launch_bounds__(256) void knn_rerank_sparse_kernel(const float* __restrict__ Q,
+                                                                const float* __restrict__ C, int mq, int mc,
+                                                                int qblocks, int nsplit, int64_t self_offset,
+                                                                const int2* __restrict__ lists,
+                                                                const int* __restrict__ counts,
+                                                                int* __restrict__ out_idx,
+                                                                float* __restrict__ out_score) {
+  const int gl = blockIdx.x * 256 + threadIdx.x;
+  const int q = gl >> 5, l = gl & 31;
+  const bool live = q < mq;
+  const int qq = live ? q : 0;
+  const int blk = qq >> 5, j = qq & 31;
+  const int64_t self_c = self_offset >= 0 ? self_offset + qq : -1;
+  const float4* qp = reinterpret_cast<const float4*>(Q + (int64_t)qq * kCols);
+  auto exact = [&](int ci) -> float {  // knn_rerank_kernel's re-score: columns 0..31 in order
+    const float4* c = reinterpret_cast<const float4*>(C + (int64_t)ci * kCols);
+    float acc = 0.0f;
+#pragma unroll
+    for (int k = 0; k < kCols / 4; ++k) {
+      const float4 v = c[k], w = qp[k];
+      acc = fmaf(w.x, v.x, acc);
+      acc = fmaf(w.y, v.y, acc);
+      acc = fmaf(w.z, v.z, acc);
+      acc = fmaf(w.w, v.w, acc);
+    }
+    return acc;
+  };
+  float bs[K];
+  int bi[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) { bs[k] = kNegBig; bi[k] = 0x7fffffff; }
+  bool over = false;
+  if (live) {
+    for (int u = l; u < 2 * nsplit; u += 32) {
+      const int64_t lb = (int64_t)(u >> 1) * qblocks + blk;
+      const int lane = j + 32 * (u & 1);
+      const int n = counts[lb * kWave + lane];
+      over |= n > kListCap;
+      const int2* li = lists + lb * kListCap * kWave + lane;
+      for (int e = 0; e < (n < kListCap ? n : kListCap); ++e) {
+        const int ci = li[(int64_t)e * kWave].y;
+        topk_insert<K>(bs, bi, exact(ci), ci);
+      }
+    }
+  }
+  // a list of the query overflowed (any of its 32 lanes saw it): exact scan of every candidate
+  const uint64_t ob = __ballot(over);
+  if (live && ((ob >> (threadIdx.x & 32)) & 0xffffffffull) != 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) { bs[k] = kNegBig; bi[k] = 0x7fffffff; }
+    for (int ci = l; ci < mc; ci += 32)
+      if (ci != self_c) topk_insert<K>(bs, bi, exact(ci), ci);
+  }
+#pragma unroll
+  for (int off = 1; off < 32; off <<= 1) {  // knn_rerank_kernel's butterfly merge, five rounds
+    float os[K];
+    int oi[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      os[k] = __shfl_xor(bs[k], off, kWave);
+      oi[k] = __shfl_xor(bi[k], off, kWave);
+    }
+    float ns[K];
+    int ni[K];
+    int ia = 0, ib = 0;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      float a = kNegBig, b = kNegBig;
+      int ai = 0x7fffffff, bj = 0x7fffffff;
+#pragma unroll
+      for (int u = 0; u < K; ++u) {
+        if (u == ia) { a = bs[u]; ai = bi[u]; }
+        if (u == ib) { b = os[u]; bj = oi[u]; }
+      }
+      const bool ta = !better(b, bj, a, ai);
+      ns[k] = ta ? a : b;
+      ni[k] = ta ? ai : bj;
+      ia += ta ? 1 : 0;
+      ib += ta ? 0 : 1;
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) { bs[k] = ns[k]; bi[k] = ni[k]; }
+  }
+  if (live && l == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      out_idx[(int64_t)q * K + k] = bi[k];
+      if (out_score) out_score[(int64_t)q * K + k] = bs[k];
+    }
+  }
+}
+
 // Merge the per-slice top-k lists of every query (same ordering: score desc, index asc).
 // lps (a power of two >= nsplit, <= 64) lanes per query: lane s loads slice s's sorted list, then
 // log2(lps) butterfly rounds merge lists pairwise through shuffles (a static-index merge of two
@@ -1761,6 +2139,57 @@ void launch_knn_topk3r(const float* Q, const void* Qhl, int mq_pad, int mq, cons
   }
 #undef FDX_KNN3R
   check_launch("knn_topk3r");
+}
+
+int knn3t_splits(int mq_pad, int mc_pad) {
+  // No slice has a fill phase, so slices cost only their prologue and their gmax / counts rows: as
+  // many as fill the resident one-wave workgroups of the passes in one round (156 / 130 VGPRs: 3 waves
+  // per SIMD, 3072 on the card -> 14 slices at 13.6k queries), >= 8 tiles each, <= 16 (the list
+  // workspace grows with every slice).  profiles/pr4_knn_twopass/lab_sweep.json: 14 is the fastest of
+  // 4 / 6 / 8 / 9 / 12 / 14 / 16 at both bench shapes; 16 needs a second round and loses 10 %.
+  static const int cap = resident_cap(knn_filter_kernel, kWave);
+  const int waves = (mq_pad / 32 + 1) / 2, tiles = mc_pad / 32;  // a wave scores two query blocks
+  int s = cap / (waves > 0 ? waves : 1);
+  if (s > 16) s = 16;
+  if (s > tiles / 8) s = tiles / 8;
+  if (s < 1) s = 1;
+  return s;
+}
+
+void launch_knn_topk3t(const float* Q, const void* Qhl, int mq_pad, int mq, const float* C, const void* Chl,
+                       const float* tmax, int mc_pad, int mc, int64_t self_offset, int k, int* out_idx,
+                       float* out_score, int* lists, int* counts, float* gmax, float* thr, int nsplit,
+                       hipStream_t stream) {
+  int2* lists2 = reinterpret_cast<int2*>(lists);
+  if (mq_pad % 32 != 0 || mc_pad % 32 != 0) throw std::runtime_error("knn_topk3t: pads must be x32");
+  if (mq > mq_pad || mc > mc_pad || nsplit < 1 || lists == nullptr || counts == nullptr || gmax == nullptr ||
+      thr == nullptr)
+    throw std::runtime_error("knn_topk3t: bad shapes or missing workspaces");
+  const int qblocks = mq_pad / 32;
+  const dim3 grid((qblocks + 1) / 2, nsplit);  // a wave scores two query blocks
+  const uint4* qh = reinterpret_cast<const uint4*>(Qhl);
+  const uint4* chl = reinterpret_cast<const uint4*>(Chl);
+  const unsigned rblocks = (unsigned)(((int64_t)mq * 32 + 255) / 256);  // 32 lanes per query
+  knn_groupmax_kernel<<<grid, kWave, 0, stream>>>(Q, qh, chl, tmax, qblocks, mc_pad, self_offset, gmax);
+#define FDX_KNN3T(KK)                                                                                       \
+  knn_threshold_kernel<KK><<<qblocks, kWave, 0, stream>>>(gmax, nsplit, mq, thr);                           \
+  knn_filter_kernel<<<grid, kWave, 0, stream>>>(Q, qh, chl, tmax, thr, qblocks, mc_pad, mc, self_offset, lists2, \
+                                                counts);                                                    \
+  knn_rerank_sparse_kernel<KK><<<rblocks, 256, 0, stream>>>(Q, C, mq, mc, qblocks, nsplit, self_offset, lists2,   \
+                                                            counts, out_idx, out_score)
+  switch (k) {
+    case 1: FDX_KNN3T(1); break;
+    case 2: FDX_KNN3T(2); break;
+    case 3: FDX_KNN3T(3); break;
+    case 4: FDX_KNN3T(4); break;
+    case 5: FDX_KNN3T(5); break;
+    case 6: FDX_KNN3T(6); break;
+    case 7: FDX_KNN3T(7); break;
+    case 8: FDX_KNN3T(8); break;
+    default: throw std::runtime_error("knn_topk3t: k must be in [1, 8]");
+  }
+#undef FDX_KNN3T
+  check_launch("knn_topk3t");
 }
 
 int knn_b3top_splits(int mq_pad, int mc_pad) {

@@ -348,6 +348,14 @@ int knn3r_splits(int mq_pad, int mc_pad);
 void launch_knn_topk3r(const float* Q, const void* Qhl, int mq_pad, int mq, const float* C, const void* Chl,
                        const float* tmax, int mc_pad, int mc, int64_t self_offset, int k, int* out_idx,
                        float* out_score, int* lists, int* counts, int nsplit, hipStream_t stream);
+// bf16x3 two-pass collect: group maxima (gmax [nsplit][mq_pad / 32][17][64] floats) -> one fixed
+// threshold per query (thr [2][mq_pad]: T, then the largest margin M) -> the filter pass that fills
+// launch_knn_topk3r's lists / counts -> the same exact re-rank
+int knn3t_splits(int mq_pad, int mc_pad);
+void launch_knn_topk3t(const float* Q, const void* Qhl, int mq_pad, int mq, const float* C, const void* Chl,
+                       const float* tmax, int mc_pad, int mc, int64_t self_offset, int k, int* out_idx,
+                       float* out_score, int* lists, int* counts, float* gmax, float* thr, int nsplit,
+                       hipStream_t stream);
 void launch_knn_topk_lds(const float* Q, int mq_pad, int mq, const float* C, int mc_pad, int mc,
                          int64_t self_offset, int k, int* out_idx, float* out_score, float* ws_score, int* ws_idx,
                          int nsplit, hipStream_t stream);

@@ -44,15 +44,34 @@ def _padded(X: torch.Tensor, n_pad: int) -> torch.Tensor:
 # (profiles/r5_x timeline): no gain.  Round 6 (profiles/r6_knn): with a quad-max pre-test in the
 # append path and the pair-interleaved MFMA chains the lab has bf16x3r at 0.184 ms vs fp32's 0.217
 # at DP=1, and in the pipeline's step (quick SGD benches, two runs each) 1.006 / 1.015 ms medians
-# against 1.037 / 1.035.  auto = bf16x3r from 8k candidates, fp32 below; FDX_KNN selects an engine.
+# against 1.037 / 1.035.
+#   bf16x3t bf16x3r's score in TWO passes with a threshold that never moves: pass 1 keeps the maximum
+#           of each of the 32 candidate groups c mod 32 per query, T = the K-th largest group maximum
+#           minus the largest margin, pass 2 lists what can reach T (~5.6 candidates per query instead
+#           of ~133) and a 32-lanes-per-query re-rank scores them exactly -- knn.hip
+#           knn_groupmax_kernel / knn_threshold_kernel / knn_filter_kernel / knn_rerank_sparse_kernel.
+#           profiles/pr4_knn_twopass: at the DP=1 self-search (13.6k x 13.6k) the lab has it at 0.128 ms
+#           against bf16x3r's 0.160 (whole call, prep included) and the plain bench's step loses 24 us;
+#           at the DP=8 global-scope rank (13.6k x 108.8k) it LOSES, 0.58 against 0.49 ms: there both
+#           passes stream the candidates at ~45 % of the MFMA rate and the second pass costs more
+#           than bf16x3r's list bookkeeping.
+# auto = fp32 below 8k candidates, bf16x3r from there -- except bf16x3t in the one range it measured
+# faster, 8k..16k candidates with at least 4k queries (nothing between 13.6k and 108.8k candidates,
+# or with fewer queries, has been measured: unchanged there); FDX_KNN selects an engine.
 KNN_BF16X3_MIN_CANDIDATES = 1 << 13
+KNN_TWOPASS_MAX_CANDIDATES = 1 << 14
+KNN_TWOPASS_MIN_QUERIES = 1 << 12
+# the engines that stream candidate tiles in fragment order (hi/lo split written by the fused prep)
+STREAM_ENGINES = ("bf16x3r", "bf16x3t", "b3top")
 
 
 def knn_engine(mq: int, mc: int, engine: str | None = None) -> str:
     e = engine or os.environ.get("FDX_KNN", "auto")
     if e == "auto":
-        return "bf16x3r" if mc >= KNN_BF16X3_MIN_CANDIDATES else "fp32"
-    if e not in ("fp32", "fp32lds", "bf16x3", "bf16x3r", "b3top"):
+        if mc < KNN_BF16X3_MIN_CANDIDATES:
+            return "fp32"
+        return "bf16x3t" if mc <= KNN_TWOPASS_MAX_CANDIDATES and mq >= KNN_TWOPASS_MIN_QUERIES else "bf16x3r"
+    if e not in ("fp32", "fp32lds", "bf16x3", "bf16x3r", "bf16x3t", "b3top"):
         raise ValueError(f"unknown k-NN engine {e!r}")
     return e
 
@@ -82,8 +101,9 @@ def knn_topk(Q: torch.Tensor, C: torch.Tensor, k: int = 5, self_offset: int = -1
     ``nsplit``: candidate slices searched by separate workgroups and merged (None = auto).
     ``engine``: "fp32" = exact fp32 MFMA chain over every candidate (16 x 32x32x2 f32 per tile);
     "bf16x3" = hi.hi + hi.lo + lo.hi bf16 MFMA filter (6 x 32x32x16 bf16 per tile) with a provable
-    margin and exact fp32 re-scoring of the survivors; None/"auto" (FDX_KNN env) picks by size.
-    Both return the exact fp32 ranking.
+    margin and exact fp32 re-scoring of the survivors; "bf16x3r" / "bf16x3t" = that filter with the
+    survivors listed and re-scored by a second kernel, under a running or a fixed threshold (see the
+    engine notes above); None/"auto" (FDX_KNN env) picks by size.  All return the exact fp32 ranking.
     ``parents`` (bf16 [mc, 32], optional): also filled with ``smote_parents(C, parents_affine)``
     by the operand-prep launch that already reads C (one launch fewer on the SMOTE path).
     ``raw_stats`` (``ScalerStats``; device self-search only, ``Q is C``): the rows are RAW padded
@@ -128,14 +148,14 @@ def knn_topk(Q: torch.Tensor, C: torch.Tensor, k: int = 5, self_offset: int = -1
     pp = _check_parents(parents, Cc, parents_affine)
     self_search = Qc.data_ptr() == Cc.data_ptr() and mq == mc and mq_pad == mc_pad
     split_done = False
-    if eng in ("bf16x3r", "b3top"):  # their hi/lo bf16 operands (+ per-tile candidate norm bound)
+    if eng in STREAM_ENGINES:  # their hi/lo bf16 operands (+ per-tile candidate norm bound)
         Qhl = torch.empty((mq_pad, 64), device=Q.device, dtype=torch.bfloat16)
         Chl = torch.empty((mc_pad, 64), device=C.device, dtype=torch.bfloat16)
         tmax = torch.empty(mc_pad // 32, device=C.device, dtype=torch.float32)
     if self_search:
         # SMOTE self-search: one launch reads the rows once and writes both operands (+ parents, and
         # for the bf16x3 engines that stream candidate tiles, their hi/lo split)
-        fuse = eng in ("bf16x3r", "b3top")
+        fuse = eng in STREAM_ENGINES
         hl = (ptr(Chl), ptr(Qhl), ptr(tmax)) if fuse else (0, 0, 0)
         if raw_stats is not None:
             st = raw_stats
@@ -155,7 +175,7 @@ def knn_topk(Q: torch.Tensor, C: torch.Tensor, k: int = 5, self_offset: int = -1
         m.knn_prep(ptr(Qc), mq, mq_pad, 1, ptr(Qp), s)
     if _operands is not None:  # the prep launch's outputs (tests)
         _operands.update(Cp=Cp, Qp=Qp)
-        if eng in ("bf16x3r", "b3top"):
+        if eng in STREAM_ENGINES:
             _operands.update(Chl=Chl, Qhl=Qhl, tmax=tmax)
     idx = torch.empty((mq, k), device=Q.device, dtype=torch.int32)
     score = torch.empty((mq, k), device=Q.device, dtype=torch.float32) if want_dist else None
@@ -163,9 +183,9 @@ def knn_topk(Q: torch.Tensor, C: torch.Tensor, k: int = 5, self_offset: int = -1
         ns = max(1, int(nsplit))
     else:
         ns = {"fp32": m.knn_splits, "fp32lds": m.knn_lds_splits, "bf16x3": m.knn3_splits,
-              "bf16x3r": m.knn3r_splits, "b3top": m.knn_b3top_splits}[eng](mq_pad, mc_pad)
+              "bf16x3r": m.knn3r_splits, "bf16x3t": m.knn3t_splits, "b3top": m.knn_b3top_splits}[eng](mq_pad, mc_pad)
     ws_s = ws_i = None
-    if ns > 1 and eng not in ("bf16x3r", "b3top"):
+    if ns > 1 and eng not in STREAM_ENGINES:
         ws_s = torch.empty((ns, mq, k), device=Q.device, dtype=torch.float32)
         ws_i = torch.empty((ns, mq, k), device=Q.device, dtype=torch.int32)
     if eng == "fp32":
@@ -180,8 +200,8 @@ def knn_topk(Q: torch.Tensor, C: torch.Tensor, k: int = 5, self_offset: int = -1
             Qhl = torch.empty((mq_pad, 64), device=Q.device, dtype=torch.bfloat16)
             Chl = torch.empty((mc_pad, 64), device=C.device, dtype=torch.bfloat16)
             tmax = torch.empty(mc_pad // 32, device=C.device, dtype=torch.float32)
-        # 2: fragment order (b3top and the bf16x3r collect stream candidate tiles; bf16x3 reads rows)
-        m.knn_split(ptr(Cp), mc_pad, 2 if eng in ("b3top", "bf16x3r") else 0, ptr(Chl), ptr(tmax), s)
+        # 2: fragment order (b3top and the bf16x3r / bf16x3t collects stream candidate tiles; bf16x3 reads rows)
+        m.knn_split(ptr(Cp), mc_pad, 2 if eng in STREAM_ENGINES else 0, ptr(Chl), ptr(tmax), s)
         m.knn_split(ptr(Qp), mq_pad, 1, ptr(Qhl), 0, s)
     if eng == "b3top":
         ns = min(ns, 32)
@@ -193,18 +213,32 @@ def knn_topk(Q: torch.Tensor, C: torch.Tensor, k: int = 5, self_offset: int = -1
                     int(k), ptr(idx), ptr(score), ptr(ws_s), ptr(ws_i), ptr(ws_m), ptr(fail), ns, s)
         if _diag is not None:  # queries answered by the exact scan (diagnostics; synchronises)
             _diag.update(nsplit=ns, exact_scans=int(fail[0].item()))
-    elif eng == "bf16x3r":
-        nb = ns * (mq_pad // 32) * 64
+    elif eng in ("bf16x3r", "bf16x3t"):
+        qb = mq_pad // 32
+        nb = ns * qb * 64
         lists = torch.empty(nb * m.KNN3R_LIST_CAP * 2, device=Q.device, dtype=torch.int32)  # (lb, index)
-        # list lengths, then each lane's final threshold and largest margin (knn_collect_kernel)
+        # list lengths, then each lane's threshold and largest margin (knn_collect_kernel: its final
+        # running threshold; knn_filter_kernel: the query's fixed T)
         counts = torch.empty(3 * nb, device=Q.device, dtype=torch.int32)
-        m.knn_topk3r(ptr(Qp), ptr(Qhl), mq_pad, mq, ptr(Cp), ptr(Chl), ptr(tmax), mc_pad, mc, int(self_offset),
-                     int(k), ptr(idx), ptr(score), ptr(lists), ptr(counts), ns, s)
-        if _diag is not None:  # list lengths (diagnostics; synchronises)
-            c = counts[:nb].float()
+        if eng == "bf16x3r":
+            m.knn_topk3r(ptr(Qp), ptr(Qhl), mq_pad, mq, ptr(Cp), ptr(Chl), ptr(tmax), mc_pad, mc, int(self_offset),
+                         int(k), ptr(idx), ptr(score), ptr(lists), ptr(counts), ns, s)
+        else:
+            gmax = torch.empty(ns * qb * 17 * 64, device=Q.device, dtype=torch.float32)  # pass 1's group maxima
+            thr = torch.empty(2 * mq_pad, device=Q.device, dtype=torch.float32)          # T, then M, per query
+            m.knn_topk3t(ptr(Qp), ptr(Qhl), mq_pad, mq, ptr(Cp), ptr(Chl), ptr(tmax), mc_pad, mc, int(self_offset),
+                         int(k), ptr(idx), ptr(score), ptr(lists), ptr(counts), ptr(gmax), ptr(thr), ns, s)
+            if _operands is not None:  # the stages' outputs (tests)
+                _operands.update(gmax=gmax.view(ns, qb, 17, 64), thr=thr.view(2, mq_pad),
+                                 lists=lists.view(ns, qb, m.KNN3R_LIST_CAP, 64, 2), counts=counts.view(3, ns, qb, 64))
+        if _diag is not None:  # list lengths and exact scans (diagnostics; synchronises)
+            cn = counts[:nb].view(ns, qb, 64)
+            c = cn.float().flatten()
+            over_q = (cn > m.KNN3R_LIST_CAP).view(ns, qb, 2, 32).any(2).any(0).flatten()[:mq]  # [query]
             _diag.update(nsplit=ns, list_cap=int(m.KNN3R_LIST_CAP), mean=float(c.mean()), max=int(c.max()),
                          p99=float(torch.quantile(c[: min(c.numel(), 1 << 24)], 0.99)),
-                         over_cap=int((c > m.KNN3R_LIST_CAP).sum()), counts=counts[:nb].view(ns, mq_pad // 32, 64))
+                         over_cap=int((c > m.KNN3R_LIST_CAP).sum()), counts=cn,
+                         per_query=float(c.sum()) / mq, exact_scans=int(over_q.sum()), scanned=over_q)
     elif eng == "bf16x3":
         m.knn_topk3(ptr(Qp), ptr(Qhl), mq_pad, mq, ptr(Cp), ptr(Chl), ptr(tmax), mc_pad, mc, int(self_offset),
                     int(k), ptr(idx), ptr(score), ptr(ws_s), ptr(ws_i), ns, s)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """k-NN (SMOTE self-search, k=5) at the bench shapes: engines x candidate slices.
 
-    python tools/knn_lab.py [--reps 20] [--engines fp32,bf16x3r] [--json out.json]
+    python tools/knn_lab.py [--reps 20] [--engines fp32,bf16x3r,bf16x3t] [--json out.json]
 
 Shapes: DP1 (the 10M-row bench's 13.6k minority rows against themselves) and the DP=8 global-scope
 rank (its 13.6k minority rows against all 8 ranks' 108.8k).  For every nsplit the event-timed
@@ -26,6 +26,8 @@ def main():
     ap.add_argument("--json", default=None)
     ap.add_argument("--splits", default="1,2,4,8,16,32")
     ap.add_argument("--engines", default="fp32")
+    ap.add_argument("--alternate", default=None, metavar="ENG[:NSPLIT],...",
+                    help="also time these engines one call each in turn, --reps rounds (medians per engine)")
     a = ap.parse_args()
     from fraud_detection_amd.data.synthetic import separable
     from fraud_detection_amd.ops import knn as K
@@ -55,7 +57,7 @@ def main():
         return float(np.median([ev[i].elapsed_time(ev[i + 1]) for i in range(a.reps)]))
 
     splitter = {"fp32": "knn_splits", "fp32lds": "knn_lds_splits", "bf16x3": "knn3_splits",
-                "bf16x3r": "knn3r_splits", "b3top": "knn_b3top_splits"}
+                "bf16x3r": "knn3r_splits", "bf16x3t": "knn3t_splits", "b3top": "knn_b3top_splits"}
     for name, (Q, Cc, off) in shapes.items():
         mq, mc = Q.shape[0], Cc.shape[0]
         ref = K.knn_topk(Q, Cc, 5, off, engine="fp32")
@@ -67,10 +69,11 @@ def main():
                 f = lambda: K.knn_topk(Q, Cc, 5, off, engine=eng, nsplit=ns)  # noqa: E731
                 got = f()
                 ms = timed(f)
-                if eng in ("bf16x3r", "b3top"):
+                if eng in ("bf16x3r", "bf16x3t", "b3top"):
                     dg = {}
                     K.knn_topk(Q, Cc, 5, off, engine=eng, nsplit=ns, _diag=dg)
                     dg.pop("counts", None)
+                    dg.pop("scanned", None)
                     print(json.dumps({name: {"engine": eng, "nsplit": ns, "lists": dg}}), flush=True)
                 case = {"engine": eng, "nsplit": ns, "ms": round(ms, 4),
                         "lists_match_frac": float((got == ref).all(1).float().mean().item()),
@@ -82,6 +85,30 @@ def main():
             base = [c for c in rec["cases"] if c["nsplit"] == auto][0]
             rec["best"], rec["auto"] = best, base
             out["shapes"][f"{name}:{eng}"] = rec
+    if a.alternate:
+        # one call of each engine per round, so drift of the card's clocks hits all of them alike
+        spec = [(e.split(":")[0], int(e.split(":")[1]) if ":" in e else None) for e in a.alternate.split(",")]
+        for name, (Q, Cc, off) in shapes.items():
+            fns = [(lambda e=e, ns=ns: K.knn_topk(Q, Cc, 5, off, engine=e, nsplit=ns)) for e, ns in spec]
+            for f in fns:
+                for _ in range(3):
+                    f()
+            ms = [[] for _ in spec]
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(a.reps * len(spec) + 1)]
+            ev[0].record()  # queued back to back (no host sync in between), as ``timed`` does
+            for r in range(a.reps):
+                for i, f in enumerate(fns):
+                    f()
+                    ev[r * len(spec) + i + 1].record()
+            torch.cuda.synchronize()
+            for r in range(a.reps):
+                for i in range(len(spec)):
+                    ms[i].append(ev[r * len(spec) + i].elapsed_time(ev[r * len(spec) + i + 1]))
+            rec = {f"{e}:{ns if ns else 'auto'}": {"median_ms": round(float(np.median(v)), 4),
+                                                   "min_ms": round(float(np.min(v)), 4)}
+                   for (e, ns), v in zip(spec, ms)}
+            out["shapes"][f"{name}:alternate"] = rec
+            print(json.dumps({name: {"alternate": rec}}), flush=True)
     if a.json:
         with open(a.json, "w") as fh:
             json.dump(out, fh, indent=1)
