@@ -326,23 +326,12 @@ void launch_knn_prep_raw(const float* Xraw, int m, int m_pad, float* out, float*
                          const KnnRawStats& st, hipStream_t stream, void* chl = nullptr, void* qhl = nullptr,
                          float* tmax = nullptr);
 int knn_splits(int mq_pad, int mc_pad);
-// bf16x3 MFMA filter + exact fp32 re-score (knn.hip): hl [m_pad][8] uint4 = hi | lo bf16 rows of
-// the prepped rows; tmax [mc_pad / 32] max candidate norm per tile (role 0 only)
+// the bf16x3 engines' operands (knn.hip): hl = hi | lo bf16 rows of the prepped rows, [m_pad][8] uint4
+// in row order (roles 0 and 1) or, role 2, per 32-row tile in the fragment order the collect kernels
+// stream; tmax [mc_pad / 32] max candidate norm per tile (candidate roles 0 and 2 only)
 void launch_knn_split(const float* Xp, int m_pad, int role, uint4* hl, float* tmax, hipStream_t stream);
-int knn3_splits(int mq_pad, int mc_pad);
-// LDS-tiled fp32 engine: workgroups of 4 waves x 32 queries share staged candidate chunks
-// (mq_pad multiple of 128)
-int knn_lds_splits(int mq_pad, int mc_pad);
 // bf16x3 collect (per-lane candidate lists [nsplit][mq_pad / 32][cap][64] int32 pairs + counts
 // [nsplit][mq_pad / 32][64]) then exact fp32 re-rank of the listed candidates (knn.hip)
-// bf16x3 scores with register top-8 approximate lists per (slice, query), then ONE merge kernel that
-// re-scores the 8 best exactly and proves the exact top-k; the queries it cannot prove go to an exact
-// scan (one workgroup each).  ws_m [nsplit][mq][2]; fail int [1 + mq] (count, query ids).
-int knn_b3top_splits(int mq_pad, int mc_pad);
-void launch_knn_b3top(const float* Q, const void* Qhl, int mq_pad, int mq, const float* C, const void* Chl,
-                      const float* tmax, int mc_pad, int mc, int64_t self_offset, int k, int* out_idx,
-                      float* out_score, float* ws_s, int* ws_i, float* ws_m, int* fail, int nsplit,
-                      hipStream_t stream);
 int knn3r_list_cap();
 int knn3r_splits(int mq_pad, int mc_pad);
 void launch_knn_topk3r(const float* Q, const void* Qhl, int mq_pad, int mq, const float* C, const void* Chl,
@@ -356,12 +345,7 @@ void launch_knn_topk3t(const float* Q, const void* Qhl, int mq_pad, int mq, cons
                        const float* tmax, int mc_pad, int mc, int64_t self_offset, int k, int* out_idx,
                        float* out_score, int* lists, int* counts, float* gmax, float* thr, int nsplit,
                        hipStream_t stream);
-void launch_knn_topk_lds(const float* Q, int mq_pad, int mq, const float* C, int mc_pad, int mc,
-                         int64_t self_offset, int k, int* out_idx, float* out_score, float* ws_score, int* ws_idx,
-                         int nsplit, hipStream_t stream);
-void launch_knn_topk3(const float* Q, const void* Qhl, int mq_pad, int mq, const float* C, const void* Chl,
-                      const float* tmax, int mc_pad, int mc, int64_t self_offset, int k, int* out_idx,
-                      float* out_score, float* ws_score, int* ws_idx, int nsplit, hipStream_t stream);
+// the fp32 engine; nsplit > 1: per-slice lists in ws_score / ws_idx [nsplit][mq][k], then merged
 void launch_knn_topk(const float* Q, int mq_pad, int mq, const float* C,
                      int mc_pad, int mc, int64_t self_offset, int k, int* out_idx,
                      float* out_score, float* ws_score, int* ws_idx, int nsplit, hipStream_t stream);

@@ -434,8 +434,7 @@ class DevicePipeline:
             class_w = (tot / (2.0 * max(tot - pos, 1.0)), tot / (2.0 * max(pos, 1.0)))
         # the fused prep runs only where the k-NN does (one process: a quota and >= 2 minority rows);
         # otherwise, and on the index-list chain, the finalize launch owed by the scaler pass goes here
-        if raw is not None and not (comm is None and n_new > 0 and n_min >= 2
-                                    and knn_ops.knn_engine(n_min, n_min) != "fp32lds"):  # (pads queries apart)
+        if raw is not None and not (comm is None and n_new > 0 and n_min >= 2):
             raw = None
         if raw is None:
             stats.finalize()

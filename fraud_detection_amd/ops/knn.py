@@ -23,46 +23,42 @@ def _padded(X: torch.Tensor, n_pad: int) -> torch.Tensor:
     return out
 
 
-# Engines (all exact fp32 rankings, tests/test_kernels_gpu.py):
+# Engines (all return the exact fp32 ranking, tests/test_kernels_gpu.py):
 #   fp32    one-wave workgroups (32 queries) streaming candidate tiles from L2 / Infinity Cache
-#           through a 16 x v_mfma_f32_32x32x2_f32 chain per 32x32 tile;
-#   fp32lds 4-wave workgroups (128 queries) sharing double-buffered LDS-staged candidate chunks
-#           (4x fewer streamed bytes, half the occupancy);
-#   bf16x3  hi.hi + hi.lo + lo.hi bf16 MFMA filter (5.3x fewer MFMA cycles) + exact re-score.
-#   bf16x3r the same filter with no fp32 work in the tile loop: passing candidates are appended to
-#           per-lane lists under a provable lower-bound threshold, and a second kernel re-scores
-#           the listed candidates exactly (8 lanes per query) -- knn.hip knn_collect_kernel.
-#   b3top   the bf16x3 score with register top-8 APPROXIMATE lists (no lists in memory, no fp32 work
-#           in the tile loop, seeded slices so ~6 waves fill every SIMD); one merge kernel re-scores
-#           each query's 8 best exactly and proves the exact top-k from the error margin (else an
-#           exact scan of that query) -- knn.hip knn_b3top_kernel.
-# Measured on MI355X from 13.6k to 170k minority rows (profiles/r2_s3i/knn_engines.jsonl): fp32
-# beat fp32lds (0.66-0.99x) and bf16x3 (0.86-0.96x) at every size.  bf16x3r (round 5,
-# profiles/r5_k, r5_o): at the DP=8 global-scope rank (13.6k queries x 108.8k candidates) 0.78 ms
-# against 1.07.  At the bench's DP=1 self-search the lab had it at 0.194 vs 0.209 ms, but inside
-# the pipeline's step its collect + re-rank took 199 us against the fp32 engine's ~200 us
-# (profiles/r5_x timeline): no gain.  Round 6 (profiles/r6_knn): with a quad-max pre-test in the
-# append path and the pair-interleaved MFMA chains the lab has bf16x3r at 0.184 ms vs fp32's 0.217
-# at DP=1, and in the pipeline's step (quick SGD benches, two runs each) 1.006 / 1.015 ms medians
-# against 1.037 / 1.035.
+#           through a 16 x v_mfma_f32_32x32x2_f32 chain per 32x32 tile, the top-k kept in registers
+#           -- knn.hip knn_topk_kernel.  auto: below 8k candidates.
+#   bf16x3r every prepped row split x = hi + lo (two bf16 rows); the tile score hi.hi + hi.lo + lo.hi
+#           (6 x v_mfma_f32_32x32x16_bf16: 5.3x fewer MFMA cycles) only filters, with no fp32 work in
+#           the tile loop: passing candidates are appended to per-lane lists under a provable
+#           lower-bound running threshold, and a second kernel re-scores the listed candidates exactly
+#           (8 lanes per query) -- knn.hip knn_collect_kernel / knn_rerank_kernel.  auto: from 8k
+#           candidates, wherever bf16x3t is not picked.  profiles/r5_k, r5_o: at the DP=8 global-scope
+#           rank (13.6k queries x 108.8k candidates) 0.78 ms against fp32's 1.07; profiles/r6_knn: with
+#           the quad-max pre-test in the append path and the pair-interleaved MFMA chains 0.184 ms
+#           against fp32's 0.217 at the DP=1 self-search (13.6k x 13.6k), and in the pipeline's step
+#           (quick SGD benches, two runs each) 1.006 / 1.015 ms medians against 1.037 / 1.035.
 #   bf16x3t bf16x3r's score in TWO passes with a threshold that never moves: pass 1 keeps the maximum
 #           of each of the 32 candidate groups c mod 32 per query, T = the K-th largest group maximum
 #           minus the largest margin, pass 2 lists what can reach T (~5.6 candidates per query instead
 #           of ~133) and a 32-lanes-per-query re-rank scores them exactly -- knn.hip
 #           knn_groupmax_kernel / knn_threshold_kernel / knn_filter_kernel / knn_rerank_sparse_kernel.
-#           profiles/pr4_knn_twopass: at the DP=1 self-search (13.6k x 13.6k) the lab has it at 0.128 ms
-#           against bf16x3r's 0.160 (whole call, prep included) and the plain bench's step loses 24 us;
-#           at the DP=8 global-scope rank (13.6k x 108.8k) it LOSES, 0.58 against 0.49 ms: there both
-#           passes stream the candidates at ~45 % of the MFMA rate and the second pass costs more
-#           than bf16x3r's list bookkeeping.
-# auto = fp32 below 8k candidates, bf16x3r from there -- except bf16x3t in the one range it measured
-# faster, 8k..16k candidates with at least 4k queries (nothing between 13.6k and 108.8k candidates,
-# or with fewer queries, has been measured: unchanged there); FDX_KNN selects an engine.
+#           auto: 8k..16k candidates with at least 4k queries, the one range it measured faster
+#           (nothing between 13.6k and 108.8k candidates, or with fewer queries, has been measured).
+#           profiles/pr4_knn_twopass: at the DP=1 self-search the lab has it at 0.128 ms against
+#           bf16x3r's 0.160 (whole call, prep included) and the plain bench's step loses 24 us; at the
+#           DP=8 global-scope rank it LOSES, 0.58 against 0.49 ms: there both passes stream the
+#           candidates at ~45 % of the MFMA rate and the second pass costs more than bf16x3r's list
+#           bookkeeping.
+# FDX_KNN (or engine=) selects one of the three.
+# Retired, each measured slower than what replaced it: fp32lds (LDS-staged candidate chunks shared by
+# 4-wave workgroups) and bf16x3 (the filter with an exact re-score inside the tile loop), 0.66-0.99x
+# and 0.86-0.96x of fp32 from 13.6k to 170k rows (profiles/r2_s3i), bf16x3 superseded by bf16x3r
+# (profiles/r5_k, r5_o); b3top (register top-8 approximate lists and a proof of exactness), 0.97 ms
+# against bf16x3r's 0.79 at the DP=8 rank (profiles/r6_knn).  profiles/pr4_knn_twopass settled the
+# set that stayed.
 KNN_BF16X3_MIN_CANDIDATES = 1 << 13
 KNN_TWOPASS_MAX_CANDIDATES = 1 << 14
 KNN_TWOPASS_MIN_QUERIES = 1 << 12
-# the engines that stream candidate tiles in fragment order (hi/lo split written by the fused prep)
-STREAM_ENGINES = ("bf16x3r", "bf16x3t", "b3top")
 
 
 def knn_engine(mq: int, mc: int, engine: str | None = None) -> str:
@@ -71,7 +67,7 @@ def knn_engine(mq: int, mc: int, engine: str | None = None) -> str:
         if mc < KNN_BF16X3_MIN_CANDIDATES:
             return "fp32"
         return "bf16x3t" if mc <= KNN_TWOPASS_MAX_CANDIDATES and mq >= KNN_TWOPASS_MIN_QUERIES else "bf16x3r"
-    if e not in ("fp32", "fp32lds", "bf16x3", "bf16x3r", "bf16x3t", "b3top"):
+    if e not in ("fp32", "bf16x3r", "bf16x3t"):
         raise ValueError(f"unknown k-NN engine {e!r}")
     return e
 
@@ -100,10 +96,10 @@ def knn_topk(Q: torch.Tensor, C: torch.Tensor, k: int = 5, self_offset: int = -1
     (ascending distance, ties -> smaller index) and optionally squared distances.
     ``nsplit``: candidate slices searched by separate workgroups and merged (None = auto).
     ``engine``: "fp32" = exact fp32 MFMA chain over every candidate (16 x 32x32x2 f32 per tile);
-    "bf16x3" = hi.hi + hi.lo + lo.hi bf16 MFMA filter (6 x 32x32x16 bf16 per tile) with a provable
-    margin and exact fp32 re-scoring of the survivors; "bf16x3r" / "bf16x3t" = that filter with the
-    survivors listed and re-scored by a second kernel, under a running or a fixed threshold (see the
-    engine notes above); None/"auto" (FDX_KNN env) picks by size.  All return the exact fp32 ranking.
+    "bf16x3r" / "bf16x3t" = a hi.hi + hi.lo + lo.hi bf16 MFMA filter (6 x 32x32x16 bf16 per tile)
+    with a provable margin, the survivors listed under a running or a fixed threshold and re-scored
+    exactly in fp32 by a second kernel (see the engine notes above); None/"auto" (FDX_KNN env) picks
+    by size.  All return the exact fp32 ranking.
     ``parents`` (bf16 [mc, 32], optional): also filled with ``smote_parents(C, parents_affine)``
     by the operand-prep launch that already reads C (one launch fewer on the SMOTE path).
     ``raw_stats`` (``ScalerStats``; device self-search only, ``Q is C``): the rows are RAW padded
@@ -125,8 +121,9 @@ def knn_topk(Q: torch.Tensor, C: torch.Tensor, k: int = 5, self_offset: int = -1
     if self_offset >= 0 and self_offset + mq > mc:
         raise ValueError("self_offset + mq exceeds the candidate set")
     if raw_stats is not None:
-        if not Q.is_cuda or Q.data_ptr() != C.data_ptr() or mq != mc or not Q.is_contiguous() or want_dist \
-                or parents_affine is not None or raw_stats.aff is None or self_offset != 0:
+        if not Q.is_cuda or Q.data_ptr() != C.data_ptr() or mq != mc or not Q.is_contiguous() \
+                or not C.is_contiguous() or want_dist or parents_affine is not None or raw_stats.aff is None \
+                or self_offset != 0:
             raise ValueError("raw_stats: a device self-search (Q is C, self_offset 0) over contiguous raw rows, "
                              "stats with aff, no parents_affine, no distances")
     if not Q.is_cuda:
@@ -138,25 +135,22 @@ def knn_topk(Q: torch.Tensor, C: torch.Tensor, k: int = 5, self_offset: int = -1
     m = native()
     s = stream_of(Q)
     eng = knn_engine(mq, mc, engine)
+    bf16 = eng != "fp32"  # bf16x3r / bf16x3t: the filter streams hi/lo bf16 candidate tiles
     mq_pad, mc_pad = _pad32(mq), _pad32(mc)
-    if eng == "fp32lds":
-        mq_pad = (mq_pad + 127) // 128 * 128  # 4 query blocks of 32 per workgroup
     Qc, Cc = Q.contiguous(), C.contiguous()
     # GEMM-ready rows: the -0.5||c||^2 term rides in column 30 (see knn.hip knn_prep_kernel)
     Qp = torch.empty((mq_pad, NCOLS), device=Q.device, dtype=torch.float32)
     Cp = torch.empty((mc_pad, NCOLS), device=C.device, dtype=torch.float32)
     pp = _check_parents(parents, Cc, parents_affine)
-    self_search = Qc.data_ptr() == Cc.data_ptr() and mq == mc and mq_pad == mc_pad
-    split_done = False
-    if eng in STREAM_ENGINES:  # their hi/lo bf16 operands (+ per-tile candidate norm bound)
+    hl = (0, 0, 0)
+    if bf16:  # the hi/lo bf16 operands (candidates in fragment order) + per-tile candidate norm bound
         Qhl = torch.empty((mq_pad, 64), device=Q.device, dtype=torch.bfloat16)
         Chl = torch.empty((mc_pad, 64), device=C.device, dtype=torch.bfloat16)
         tmax = torch.empty(mc_pad // 32, device=C.device, dtype=torch.float32)
-    if self_search:
+        hl = (ptr(Chl), ptr(Qhl), ptr(tmax))
+    if Qc.data_ptr() == Cc.data_ptr() and mq == mc:
         # SMOTE self-search: one launch reads the rows once and writes both operands (+ parents, and
-        # for the bf16x3 engines that stream candidate tiles, their hi/lo split)
-        fuse = eng in STREAM_ENGINES
-        hl = (ptr(Chl), ptr(Qhl), ptr(tmax)) if fuse else (0, 0, 0)
+        # for the bf16x3 engines their hi/lo split)
         if raw_stats is not None:
             st = raw_stats
             f = st.take_pending()  # the finalize still owed: folded into this launch
@@ -167,53 +161,30 @@ def knn_topk(Q: torch.Tensor, C: torch.Tensor, k: int = 5, self_offset: int = -1
                            ptr(st.mean32), ptr(st.inv32), ptr(st.aff), *hl)
         else:
             m.knn_prep(ptr(Cc), mc, mc_pad, 2, ptr(Cp), s, ptr(Qp), ptr(parents_affine), pp, *hl)
-        split_done = fuse
     else:
-        if raw_stats is not None:
-            raise ValueError("raw_stats: the fp32lds engine pads its queries apart from the candidates")
         m.knn_prep(ptr(Cc), mc, mc_pad, 0, ptr(Cp), s, 0, ptr(parents_affine), pp)
         m.knn_prep(ptr(Qc), mq, mq_pad, 1, ptr(Qp), s)
+        if bf16:  # the split the fused prep did not write: role 2 = candidates, 1 = queries
+            m.knn_split(ptr(Cp), mc_pad, 2, ptr(Chl), ptr(tmax), s)
+            m.knn_split(ptr(Qp), mq_pad, 1, ptr(Qhl), 0, s)
     if _operands is not None:  # the prep launch's outputs (tests)
         _operands.update(Cp=Cp, Qp=Qp)
-        if eng in STREAM_ENGINES:
+        if bf16:
             _operands.update(Chl=Chl, Qhl=Qhl, tmax=tmax)
     idx = torch.empty((mq, k), device=Q.device, dtype=torch.int32)
     score = torch.empty((mq, k), device=Q.device, dtype=torch.float32) if want_dist else None
     if nsplit is not None:
         ns = max(1, int(nsplit))
     else:
-        ns = {"fp32": m.knn_splits, "fp32lds": m.knn_lds_splits, "bf16x3": m.knn3_splits,
-              "bf16x3r": m.knn3r_splits, "bf16x3t": m.knn3t_splits, "b3top": m.knn_b3top_splits}[eng](mq_pad, mc_pad)
-    ws_s = ws_i = None
-    if ns > 1 and eng not in STREAM_ENGINES:
-        ws_s = torch.empty((ns, mq, k), device=Q.device, dtype=torch.float32)
-        ws_i = torch.empty((ns, mq, k), device=Q.device, dtype=torch.int32)
+        ns = {"fp32": m.knn_splits, "bf16x3r": m.knn3r_splits, "bf16x3t": m.knn3t_splits}[eng](mq_pad, mc_pad)
     if eng == "fp32":
+        ws_s = ws_i = None
+        if ns > 1:  # the slices' lists, merged by a second kernel
+            ws_s = torch.empty((ns, mq, k), device=Q.device, dtype=torch.float32)
+            ws_i = torch.empty((ns, mq, k), device=Q.device, dtype=torch.int32)
         m.knn_topk(ptr(Qp), mq_pad, mq, ptr(Cp), mc_pad, mc, int(self_offset), int(k), ptr(idx),
                    ptr(score), ptr(ws_s), ptr(ws_i), ns, s)
-    elif eng == "fp32lds":
-        m.knn_topk_lds(ptr(Qp), mq_pad, mq, ptr(Cp), mc_pad, mc, int(self_offset), int(k), ptr(idx),
-                       ptr(score), ptr(ws_s), ptr(ws_i), ns, s)
-    elif not split_done:
-        # hi/lo bf16 split of both operands (+ per-tile candidate norm bound) for the filter
-        if eng == "bf16x3":
-            Qhl = torch.empty((mq_pad, 64), device=Q.device, dtype=torch.bfloat16)
-            Chl = torch.empty((mc_pad, 64), device=C.device, dtype=torch.bfloat16)
-            tmax = torch.empty(mc_pad // 32, device=C.device, dtype=torch.float32)
-        # 2: fragment order (b3top and the bf16x3r / bf16x3t collects stream candidate tiles; bf16x3 reads rows)
-        m.knn_split(ptr(Cp), mc_pad, 2 if eng in STREAM_ENGINES else 0, ptr(Chl), ptr(tmax), s)
-        m.knn_split(ptr(Qp), mq_pad, 1, ptr(Qhl), 0, s)
-    if eng == "b3top":
-        ns = min(ns, 32)
-        ws_s = torch.empty((ns, mq, 8), device=Q.device, dtype=torch.float32)
-        ws_i = torch.empty((ns, mq, 8), device=Q.device, dtype=torch.int32)
-        ws_m = torch.empty((ns, mq, 2), device=Q.device, dtype=torch.float32)
-        fail = torch.empty(1 + mq, device=Q.device, dtype=torch.int32)  # count, then failed query ids
-        m.knn_b3top(ptr(Qp), ptr(Qhl), mq_pad, mq, ptr(Cp), ptr(Chl), ptr(tmax), mc_pad, mc, int(self_offset),
-                    int(k), ptr(idx), ptr(score), ptr(ws_s), ptr(ws_i), ptr(ws_m), ptr(fail), ns, s)
-        if _diag is not None:  # queries answered by the exact scan (diagnostics; synchronises)
-            _diag.update(nsplit=ns, exact_scans=int(fail[0].item()))
-    elif eng in ("bf16x3r", "bf16x3t"):
+    else:
         qb = mq_pad // 32
         nb = ns * qb * 64
         lists = torch.empty(nb * m.KNN3R_LIST_CAP * 2, device=Q.device, dtype=torch.int32)  # (lb, index)
@@ -239,9 +210,6 @@ def knn_topk(Q: torch.Tensor, C: torch.Tensor, k: int = 5, self_offset: int = -1
                          p99=float(torch.quantile(c[: min(c.numel(), 1 << 24)], 0.99)),
                          over_cap=int((c > m.KNN3R_LIST_CAP).sum()), counts=cn,
                          per_query=float(c.sum()) / mq, exact_scans=int(over_q.sum()), scanned=over_q)
-    elif eng == "bf16x3":
-        m.knn_topk3(ptr(Qp), ptr(Qhl), mq_pad, mq, ptr(Cp), ptr(Chl), ptr(tmax), mc_pad, mc, int(self_offset),
-                    int(k), ptr(idx), ptr(score), ptr(ws_s), ptr(ws_i), ns, s)
     if want_dist:
         if _operands is not None:  # the engine's own scores q.c - 0.5||c||^2 (tests)
             _operands.update(score=score)

@@ -185,16 +185,6 @@ def filter_pass(approx, margin, k, self_offset=-1):
     return (a + margin) >= thr[:, None]
 
 
-def filter_pass_exact_threshold(approx, margin, s, k):
-    """[mq, mc] bool: the bf16x3 engine's filter at its final threshold: the threshold is the EXACT
-    k-th best score s_k (its lists hold re-scored candidates) and a candidate passes when
-    approx >= s_k - 2 m (its margin is 2^-13 (..) = 2 m).  Unlike ``filter_pass`` this compares an
-    approximate score with an exact one, so it also sees an error common to all candidates; b3top's
-    proof s_k > a_P + M is of the same kind.  ``s`` carries -inf on the self column."""
-    sk = -np.partition(-s, k - 1, axis=1)[:, k - 1][:, None]
-    return (approx >= sk - 2.0 * margin) & np.isfinite(s)
-
-
 def filtered_topk(passed, s, k):
     """What the exact re-rank returns from the candidates that passed: their fp64 top-k (ties ->
     smaller index).  ``s`` carries -inf on the self column."""

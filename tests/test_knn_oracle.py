@@ -5,57 +5,54 @@ approximate score hi.hi + hi.lo + lo.hi is within 2^-16 sum|q_f c_f| of the exac
 m = 2^-14 (||q|| tmax + 0.5 tmax^2) is at least 4x that, the running threshold never exceeds the exact
 k-th best.  A device test pins those links only on inputs where breaking one changes the answer or a
 checked intermediate.  These tests state that for the committed seeds, with an fp64 emulation
-(_knn_cases.py) of the two filter forms at their FINAL threshold:
-  collect  (bf16x3r, the auto engine): threshold = the k-th best lower bound approx - m, a candidate
-           passes when approx + m reaches it.  Approximate scores are compared with each other only.
-  exact    (bf16x3; b3top's proof is of this kind): threshold = the exact k-th best s_k, a candidate
-           passes when approx >= s_k - 2 m.  An error common to all candidates counts in full.
+(_knn_cases.py) of the collect filter (bf16x3r, the auto engine) at its FINAL threshold: the
+threshold is the k-th best lower bound approx - m, a candidate passes when approx + m reaches it.
+Approximate scores are compared with each other only.  (The fixed-threshold rule of bf16x3t has its
+own emulation: test_knn_twopass_oracle.py.)
 
 Measured (k = 5, self-search).  err = max |approx3 - exact| / m, asserted <= 0.25; then the share of
 queries whose re-ranked answer ``assert_valid_topk`` rejects when the filter is hi-only (both lo
-halves lost), has lost the query's lo half, or uses m / 64 -- collect form / exact form:
+halves lost), has lost the query's lo half, or uses m / 64:
 
-  case          err     hi-only           no query lo       m / 64
-  normal        0.065    2.1 % / 38.8 %   0.1 % / 19.1 %    0 % /  0.3 %
-  cluster3      0.061   65.0 % / 90.3 %   0   % / 84.0 %    0 % / 11.3 %
-  cluster30     0.079   29.7 % / 56.0 %   0   % / 35.7 %    0 % /  4.0 %
-  cluster3_far  0.101   93.0 % / 94.0 %   0   % / 47.0 %    0 % / 85.3 %
-  heavy         0.184    2.3 % / 20.2 %   0   % /  7.6 %    0 % /  1.0 %
-  near_origin   0.054    1.8 % / 35.4 %   0.3 % / 16.2 %    0 % /  0.6 %
-  lattice       0.151   60.5 % / 59.6 %   0   % / 44.1 %    0 % / 14.1 %
-  (with the intact filter: 0 % everywhere, both forms)
+  case          err     hi-only   no query lo   m / 64
+  normal        0.065    2.1 %    0.1 %         0 %
+  cluster3      0.061   65.0 %    0   %         0 %
+  cluster30     0.079   29.7 %    0   %         0 %
+  cluster3_far  0.101   93.0 %    0   %         0 %
+  heavy         0.184    2.3 %    0   %         0 %
+  near_origin   0.054    1.8 %    0.3 %         0 %
+  lattice       0.151   60.5 %    0   %         0 %
+  (with the intact filter: 0 % everywhere)
 
-  * hi-only is caught by the ranking itself on the clusters, under either form, and a true neighbour
-    is then left out by more than 2 tol (cluster3: 65 %).  Under the auto engine's collect form
-    ``normal`` shows it for 2.1 % of the queries -- 0.4 % of the returned entries, inside the 0.99
-    entry-match bar of the older continuous tests -- and a lost query lo for 0.1 %: ``normal`` alone is
-    not a test.
-  * A lost query lo half is caught on cluster3_far under the exact form (47.0 %).  The collect form's
-    ranking cannot see it (0 %): the error lo_q . c is lo_q . b, the same for every candidate of a
-    cluster b + P, plus lo_q . P_c, about 2^-9 |q_f| |P_c| ~ 0.01 against m = 0.023, and a shift common
-    to all scores moves the threshold with them.  For that engine the device test bounds the ABSOLUTE
-    error of the scores b3top keeps (same operands, same MFMA chain) by m / 4 + tol and checks that
-    every listed lower bound is one: with the query lo lost, 96.7 % of cluster3_far's queries (100 %
-    of cluster3's, 99.8 % of heavy's) have one of their 8 best approximate scores off by more.
-  * m / 64 is caught on cluster3_far under the exact form (85.3 %) and, for the collect form, on
-    ``lattice``: its tight queries have >= 493 candidates inside the true margin (both list lanes
-    overflow, no b3top proof holds); with m / 64 only 31.5 on average (max 142) pass, 80 % of them stay
-    within ONE lane's 64 entries, and the b3top proof s_k > a_8 + m wrongly holds for 42 % -- the
-    device test's "the over-cap lanes are exactly the tight queries' lanes" and "exact_scans >= the
-    tight queries" both fail.
+  * hi-only is caught by the ranking itself on the clusters, and a true neighbour is then left out by
+    more than 2 tol (cluster3: 65 %).  ``normal`` shows it for 2.1 % of the queries -- 0.4 % of the
+    returned entries, inside the 0.99 entry-match bar of the older continuous tests -- and a lost
+    query lo for 0.1 %: ``normal`` alone is not a test.
+  * A lost query lo half is not seen by the ranking (0 %): on cluster3_far the error lo_q . c is
+    lo_q . b, the same for every candidate of a cluster b + P, plus lo_q . P_c, about
+    2^-9 |q_f| |P_c| ~ 0.01 against m = 0.023, and a shift common to all scores moves the threshold
+    with them.  The ABSOLUTE error of the best approximate scores sees it: with the query lo lost,
+    96.7 % of cluster3_far's queries (100 % of cluster3's, 99.8 % of heavy's) have one of their 8
+    best approximate scores off by more than m / 4 + tol.  The device tests hold the approximate
+    scores they read back to that bound -- every two-pass group maximum within m / 4 of the intact
+    emulation (test_knn_twopass_gpu.py) -- and check that every listed lower bound is one.
+  * m / 64 is not seen by the ranking on the clusters either (0 %); it is caught on ``lattice``: its
+    tight queries have >= 493 candidates inside the true margin (both list lanes overflow); with
+    m / 64 only 31.5 on average (max 142) pass and 80 % of them stay within ONE lane's 64 entries --
+    the device test's "the over-cap lanes are exactly the tight queries' lanes" fails.
 
 Path coverage on ``lattice`` (nsplit = 1): the 501 tight queries (the 500 rows built tight and the
 corner row that lent them its columns 4..29; the same set for k = 1, 5, 8) have >= 493 passing
 candidates, >= 213 per list lane for certain; the spread queries 5.5 on average (max 9), and at most
-63 per lane even under the lowest running threshold without compaction; the emulated b3top proof
-holds for 99.7 % of the spread queries and for no tight query.  3.6 % of the lattice's feature entries
-have lo != 0 (6.5 % of all prepped entries), 419 rows repeat an earlier one, and both fp32 chain
-orders (columns 0..31; feature 16h + s at MFMA step s) reproduce the fp64 score bit for bit.
+63 per lane even under the lowest running threshold without compaction.  3.6 % of the lattice's
+feature entries have lo != 0 (6.5 % of all prepped entries), 419 rows repeat an earlier one, and both
+fp32 chain orders (columns 0..31; feature 16h + s at MFMA step s) reproduce the fp64 score bit for bit.
 
-Checked against the device once, with deliberately broken builds that are not part of the tree: a
-split that zeroes every lo half fails 40 of the 53 device tests, one that zeroes the queries' lo half
-33, margins scaled by 1/64 (kMarginScale and bf16x3's 2^-13) 14 -- in each case the engine tests on
-the cluster cases and the lattice, the fallback tests and the proof-invariant tests among them."""
+Checked against the device once, with deliberately broken builds that are not part of the tree, when
+the suite still ran three more engines (since retired) and had 53 device tests: a split that zeroes
+every lo half failed 40 of them, one that zeroes the queries' lo half 33, margins scaled by 1/64 14
+-- in each case the engine tests on the cluster cases and the lattice, the fallback tests and the
+proof-invariant tests among them."""
 import numpy as np
 import pytest
 
@@ -65,26 +62,22 @@ from fraud_detection_amd.ops import reference as ref
 K = 5
 
 
-def _emulated(name, kind="approx3", scale=1.0, form="collect"):
-    """(approx, margin, pass mask, re-ranked answer) of the self-search of one case under one of the
-    two filter forms: ``collect`` (bf16x3r: threshold = k-th best LOWER BOUND) or ``exact``
-    (bf16x3: threshold = exact k-th best score)."""
+def _emulated(name, kind="approx3", scale=1.0):
+    """(approx, margin, pass mask, re-ranked answer) of the self-search of one case under the collect
+    filter (bf16x3r: threshold = k-th best LOWER BOUND)."""
     X = KC.case(name)
     s, _ = KC.oracle(name)
     mg = KC.margins(X, X) * scale
     a = KC.approx_scores(X, X, kind)
-    if form == "collect":
-        p = KC.filter_pass(a, mg, K, 0) & np.isfinite(s)
-    else:
-        p = KC.filter_pass_exact_threshold(a, mg, s, K)
+    p = KC.filter_pass(a, mg, K, 0) & np.isfinite(s)
     return a, mg, p, KC.filtered_topk(p, s, K)
 
 
-def _lost_share(name, kind, scale=1.0, form="collect"):
+def _lost_share(name, kind, scale=1.0):
     """Share of queries whose re-ranked answer ``assert_valid_topk`` rejects (a true neighbour left out
     beyond the tolerance)."""
     s, t = KC.oracle(name)
-    return float(KC.outsider_violations(_emulated(name, kind, scale, form)[3], s, t).mean())
+    return float(KC.outsider_violations(_emulated(name, kind, scale)[3], s, t).mean())
 
 
 # ---- exactness on the lattice -----------------------------------------------------------------
@@ -129,11 +122,10 @@ def test_intact_filter_loses_nothing(name):
     assert not np.isinf(np.take_along_axis(s, idx, 1)).any()
 
 
-# ---- power under the emulated final-threshold filters ------------------------------------------
+# ---- power under the emulated final-threshold filter -------------------------------------------
 def test_hi_only_filter_is_caught_on_the_clusters():
-    for form, c3, c30 in (("collect", 0.65, 0.296), ("exact", 0.903, 0.56)):  # measured
-        assert _lost_share("cluster3", "approx_hi_only", form=form) >= 0.25
-        assert _lost_share("cluster30", "approx_hi_only", form=form) >= 0.10
+    assert _lost_share("cluster3", "approx_hi_only") >= 0.25   # measured 65.0 %
+    assert _lost_share("cluster30", "approx_hi_only") >= 0.10  # measured 29.7 %
     # "by more than 2 tol", stated directly: the kept k-th best is below the true one by over twice
     # the largest tolerance of the kept list
     s, t = KC.oracle("cluster3")
@@ -145,8 +137,6 @@ def test_hi_only_filter_is_caught_on_the_clusters():
 
 
 def test_lost_query_lo_is_caught_on_cluster3_far():
-    # against an exact threshold (bf16x3; b3top's proof) the error lo_q . c counts in full
-    assert _lost_share("cluster3_far", "approx_no_query_lo", form="exact") >= 0.20   # measured 47.0 %
     # the collect filter compares approximate scores with each other, and lo_q . b is common to every
     # candidate of a cluster b + P: its ranking does not see it (measured 0 %) ...
     assert _lost_share("cluster3_far", "approx_no_query_lo") < 0.01
@@ -156,11 +146,6 @@ def test_lost_query_lo_is_caught_on_cluster3_far():
     assert _kept_error_share("heavy", "approx_no_query_lo") >= 0.20          # measured 99.8 %
     for name in ("cluster3_far", "cluster3", "heavy"):
         assert _kept_error_share(name, "approx3") == 0.0
-
-
-def test_margin_over_64_is_caught_on_cluster3_far():
-    assert _lost_share("cluster3_far", "approx3", 1.0 / 64, form="exact") >= 0.20    # measured 85.3 %
-    assert _lost_share("cluster3_far", "approx3", 1.0 / 64) < 0.01                   # collect form: 0 %
 
 
 def test_normal_alone_is_not_a_test():
@@ -175,7 +160,8 @@ def test_normal_alone_is_not_a_test():
 
 def _kept_error_share(name, kind):
     """Share of queries with one of their 8 best approximate scores off by more than margin / 4 + tol
-    (the bound the device test puts on b3top's kept scores)."""
+    (the quarter margin the proof allows |approx - exact|; the device tests hold the approximate scores
+    they read back, the two-pass group maxima, to it)."""
     X = KC.case(name)
     s, t = KC.oracle(name)
     a = np.where(np.isfinite(s), KC.approx_scores(X, X, kind), -np.inf)
@@ -186,17 +172,12 @@ def _kept_error_share(name, kind):
 
 # ---- path coverage on the lattice (nsplit = 1) ------------------------------------------------
 def _lattice_paths(scale=1.0):
-    X, tight = KC.case("lattice"), KC.lattice_tight()
-    s, _ = KC.oracle("lattice")
-    a, mg, p, _ = _emulated("lattice", scale=scale)
-    a = np.where(np.isfinite(s), a, -np.inf)
-    a8 = -np.partition(-a, 7, axis=1)[:, 7]
-    sk = -np.partition(-s, K - 1, axis=1)[:, K - 1]
-    return tight, p.sum(1), sk > a8 + mg.max(1)
+    """(the tight queries, the number of candidates that pass the final-threshold filter per query)"""
+    return KC.lattice_tight(), _emulated("lattice", scale=scale)[2].sum(1)
 
 
 def test_lattice_reaches_the_fallback_paths_for_tight_queries_only():
-    tight, cnt, proof = _lattice_paths()
+    tight, cnt = _lattice_paths()
     built = KC.lattice_built_tight()
     # the 500 rows built tight and the corner row that lent them its columns 4..29
     assert built.sum() == 500 and np.all(tight[built]) and tight.sum() == 501
@@ -204,8 +185,6 @@ def test_lattice_reaches_the_fallback_paths_for_tight_queries_only():
         assert np.array_equal(KC.lattice_tight(k), tight)
     assert cnt[tight].min() > 2 * 64, int(cnt[tight].min())           # measured 493
     assert cnt[~tight].mean() < 10 and cnt[~tight].max() < 64, (cnt[~tight].mean(), cnt[~tight].max())  # 5.5, 9
-    assert proof[~tight].mean() >= 0.90, float(proof[~tight].mean())  # measured 99.7 %
-    assert not proof[tight].any()
     # per list lane (a query's candidates are shared by two lanes, rows 4h .. 4h + 3 of every 8):
     # a tight query overflows BOTH 64-entry lanes whatever the approximate error is, every other
     # query fits both at the final threshold ...
@@ -230,11 +209,11 @@ def test_lattice_reaches_the_fallback_paths_for_tight_queries_only():
 
 
 def test_margin_over_64_is_caught_on_the_lattice():
-    tight, cnt, proof = _lattice_paths(1.0 / 64)
-    # most tight queries no longer overflow their two 64-entry lanes (measured mean 31.5, max 142) ...
+    tight, cnt = _lattice_paths(1.0 / 64)
+    # most tight queries no longer overflow their two 64-entry lanes (measured mean 31.5, max 142)
     assert np.mean(cnt[tight] <= 64) >= 0.5, float(np.mean(cnt[tight] <= 64))
-    # ... and the b3top proof wrongly holds for many of them (measured 42 %)
-    assert proof[tight].mean() >= 0.2, float(proof[tight].mean())
+    # the ranking alone would not show it, here or on the far cluster (measured 0 %)
+    assert _lost_share("cluster3_far", "approx3", 1.0 / 64) < 0.01
 
 
 # ---- the checker itself -----------------------------------------------------------------------

@@ -161,7 +161,12 @@ def _check_prep(m, d, engine, fold, dev):
     assert st1.pending is None
     assert sorted(ops0) == sorted(ops1) and ("Chl" in ops0) == (engine != "fp32")
     for name in ops0:
-        assert torch.equal(_bits(ops1[name]), _bits(ops0[name])), name
+        a, b = ops1[name], ops0[name]
+        if name == "lists":  # bf16x3t's [slice][block][entry][lane]: a lane writes its first counts[0] entries only
+            assert torch.equal(ops1["counts"], ops0["counts"])
+            live = torch.arange(a.shape[2], device=dev)[None, None, :, None] < ops0["counts"][0][:, :, None, :]
+            a, b = a[live], b[live]
+        assert torch.equal(_bits(a), _bits(b)), name
     assert torch.equal(_bits(par1), _bits(par0))
     assert torch.equal(nbr1, nbr0)
     _assert_stats_equal(st1, st0)
@@ -174,7 +179,7 @@ def test_fused_prep_matches_chain(dev, engine, m, d):
     _check_prep(m, d, engine, True, dev)
 
 
-@pytest.mark.parametrize("engine,m,d,fold", [("b3top", 1000, 30, True), ("b3top", 33, 7, True),
+@pytest.mark.parametrize("engine,m,d,fold", [("bf16x3t", 1000, 30, True), ("bf16x3t", 33, 7, True),
                                              ("bf16x3r", 33, 30, False), ("fp32", 1000, 7, False)])
 def test_fused_prep_other_forms(dev, engine, m, d, fold):
     _check_prep(m, d, engine, fold, dev)

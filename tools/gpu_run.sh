@@ -125,9 +125,9 @@ for st in "$@"; do
     pmcknn)  # bf16x3r collect / rerank counters (FDX_KNN_ARGS picks engines and splits)
       cd /tmp && export TMPDIR=/tmp
       # shellcheck disable=SC2086
-      step pmcknn_a 180 rocprofv3 --kernel-include-regex "knn_(collect|rerank|topk_kernel|b3top)" --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_VMEM SQ_INSTS_SALU --output-format csv -d "$OUT/pmcknn_a" -o run -- python3 "$R/tools/knn_lab.py" --reps 3 $FDX_KNN_ARGS || exit 1
+      step pmcknn_a 180 rocprofv3 --kernel-include-regex "knn_(collect|rerank|topk_kernel)" --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_VMEM SQ_INSTS_SALU --output-format csv -d "$OUT/pmcknn_a" -o run -- python3 "$R/tools/knn_lab.py" --reps 3 $FDX_KNN_ARGS || exit 1
       # shellcheck disable=SC2086
-      step pmcknn_b 180 rocprofv3 --kernel-include-regex "knn_(collect|rerank|topk_kernel|b3top)" --pmc SQ_INSTS_LDS SQ_WAIT_ANY SQ_ACTIVE_INST_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_INST_CYCLES_VMEM SQ_ACTIVE_INST_ANY --output-format csv -d "$OUT/pmcknn_b" -o run -- python3 "$R/tools/knn_lab.py" --reps 3 $FDX_KNN_ARGS
+      step pmcknn_b 180 rocprofv3 --kernel-include-regex "knn_(collect|rerank|topk_kernel)" --pmc SQ_INSTS_LDS SQ_WAIT_ANY SQ_ACTIVE_INST_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_INST_CYCLES_VMEM SQ_ACTIVE_INST_ANY --output-format csv -d "$OUT/pmcknn_b" -o run -- python3 "$R/tools/knn_lab.py" --reps 3 $FDX_KNN_ARGS
       cd "$R" ;;
     knndepth)  # bf16x3r collect: 2 vs 4 candidate tiles in flight (FDX_KNN3R_DEPTH), lab at DP1 / DP8 shapes
       step knndepth_4 300 env FDX_KNN3R_DEPTH=4 python tools/knn_lab.py --engines bf16x3r --splits 2,4,8 --json "$OUT/knndepth_4.json" &&

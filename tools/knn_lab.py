@@ -56,20 +56,18 @@ def main():
         torch.cuda.synchronize()
         return float(np.median([ev[i].elapsed_time(ev[i + 1]) for i in range(a.reps)]))
 
-    splitter = {"fp32": "knn_splits", "fp32lds": "knn_lds_splits", "bf16x3": "knn3_splits",
-                "bf16x3r": "knn3r_splits", "bf16x3t": "knn3t_splits", "b3top": "knn_b3top_splits"}
+    splitter = {"fp32": "knn_splits", "bf16x3r": "knn3r_splits", "bf16x3t": "knn3t_splits"}
     for name, (Q, Cc, off) in shapes.items():
         mq, mc = Q.shape[0], Cc.shape[0]
         ref = K.knn_topk(Q, Cc, 5, off, engine="fp32")
         for eng in a.engines.split(","):
-            mqp = (mq + 31) // 32 * 32 if eng != "fp32lds" else (mq + 127) // 128 * 128
-            auto = getattr(native(), splitter[eng])(mqp, (mc + 31) // 32 * 32)
+            auto = getattr(native(), splitter[eng])((mq + 31) // 32 * 32, (mc + 31) // 32 * 32)
             rec = {"engine": eng, "mq": mq, "mc": mc, "auto_nsplit": int(auto), "cases": []}
             for ns in sorted({int(v) for v in a.splits.split(",")} | {int(auto)}):
                 f = lambda: K.knn_topk(Q, Cc, 5, off, engine=eng, nsplit=ns)  # noqa: E731
                 got = f()
                 ms = timed(f)
-                if eng in ("bf16x3r", "bf16x3t", "b3top"):
+                if eng != "fp32":
                     dg = {}
                     K.knn_topk(Q, Cc, 5, off, engine=eng, nsplit=ns, _diag=dg)
                     dg.pop("counts", None)
