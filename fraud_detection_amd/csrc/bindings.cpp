@@ -788,6 +788,16 @@ PYBIND11_MODULE(_fdx_native, m) {
   m.def("sgd_persist_blocks", [](int grid_blocks) { return fdx::sgd_persist_blocks(grid_blocks); });
   m.def("sgd_full_blocks", []() { return fdx::sgd_full_blocks(); });
   m.attr("SGD_PERSIST_WORDS") = fdx::kSgdPersistWords;
+  {  // logreg.hip's SGD shapes, read-only
+    const fdx::SgdConstants k = fdx::sgd_constants();
+    m.attr("SGD_REPLICAS") = k.replicas;
+    m.attr("SGD_GROUPS") = k.groups;
+    m.attr("SGD_LOADS") = k.loads;
+    m.attr("SGD_PERSIST_WAVES") = k.persist_waves;
+    m.attr("SGD_PERSIST_REPLICAS") = k.persist_replicas;
+    m.attr("SGD_SYN_Q") = k.syn_q;
+    m.attr("SGD_SYN_QL") = k.syn_ql;
+  }
   // Data parallel lean step: FISH pass -> fixed-point sums[36] (int64) for the all-reduce, then the
   // update from the reduced sums.
   m.def("sgd_pass_sums", [smote_view](u X, int fp8, float x_scale, int64_t end, u w32, u cw, u done, int nb, int b,

@@ -255,6 +255,14 @@ void launch_sgd_update_fixed(const long long* sums, double* state, float* w32, i
 // The SGD pass grid (its waves define the minibatch partition): 2 x 256-thread blocks per CU, so
 // that the persistent launch holds it as one 8-wave block per CU.
 int sgd_full_blocks();
+// The SGD kernels' compile-time shapes, read-only (tests size their cases from them): accumulator
+// replicas of the per-step and the persistent launch, sgd_step_kernel's row groups and loads per
+// thread, waves per persistent block, the fixed-point scales of the virtual samples' terms.
+struct SgdConstants {
+  int replicas, groups, loads, persist_waves, persist_replicas;
+  double syn_q, syn_ql;
+};
+SgdConstants sgd_constants();
 constexpr int kSgdMaxEpochs = 8;
 // barrier shards (1 KB) | 3 accumulator sets | fault word | backup of the initial state + weights + done
 // (logreg.hip kWs*: static_assert that it fits)

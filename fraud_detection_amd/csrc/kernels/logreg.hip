@@ -60,7 +60,7 @@ __device__ __forceinline__ void unpack8(const uint4& v, float x[8]) {
 // point (int64), so the bucket order the fill's atomics produce does not change a bit: fits stay
 // bitwise reproducible.
 constexpr float kSynQ = 4194304.0f;   // 2^22: r, r lam, d, d lam, d lam^2 (|v| <= s <= 32)
-constexpr float kSynQL = 16384.0f;    // 2^14: per-sample loss (<= 80 s)
+constexpr float kSynQL = 16384.0f;    // 2^14: per-sample loss (<= 80 s; what lies beyond: per pick)
 
 template <int G>
 __device__ __forceinline__ long long group_sum_i64(long long v) {
@@ -190,6 +190,28 @@ __device__ __forceinline__ void pick_compute(const SmoteView& sv, const PickIn<L
       if constexpr (HESS || FISH) sd += bd;
       if constexpr (HESS) { sdl += bdl; sdll += bdll; }
     }
+  }
+  // The clamp above keeps every fixed-point term in range, but it also cuts a sample's loss at
+  // 80 s, where a stored row's loss keeps growing as -z.  z is linear in lambda, so samples
+  // below the clamp exist only when a parent's logit is (rare: a model wrong by 80 logits on a
+  // minority row); then the missing s sum (-80 - z) = s (n (-80 - za) - dz sum lam) over those
+  // samples.  The branch is uniform over the pick's LPR lanes (za, zb are group sums).  Their count
+  // n and lambda sum are integers, summed over the lanes FIRST; the term is then rounded to fixed
+  // point ONCE per pick and added in one lane -- a function of the pick's sample set only, whatever
+  // order the bucket fill dealt the lambdas to the lanes in (one rounding of 0.5 / kSynQL per pick).
+  if (fminf(za, zb) < -80.0f) {
+    long long n_lo = 0, l_lo = 0;
+    for (int j = q; j < cnt; j += LPR) {
+      const uint32_t li = sv.lam[o0 + j];
+      if (fmaf((float)li * (1.0f / 65536.0f), dz, za) < -80.0f) {
+        n_lo += 1;
+        l_lo += (long long)li;
+      }
+    }
+    n_lo = group_sum_i64<LPR>(n_lo);
+    l_lo = group_sum_i64<LPR>(l_lo);
+    const double cut = (double)n_lo * (-80.0 - (double)za) - (double)dz * ((double)l_lo * (1.0 / 65536.0));
+    if (q == 0) sl += (long long)__builtin_rint((double)sw1 * cut * (double)kSynQL);
   }
   sr = group_sum_i64<LPR>(sr);
   srl = group_sum_i64<LPR>(srl);
@@ -1540,10 +1562,11 @@ enum : int { kAvg = 160, kEpG = 192, kEpLoss = 224, kEpW = 225, kNAvg = 226, kDb
 constexpr double kDbarFloor = 1e-3;  // lr_t <= c / 1e-3: a saturated minibatch cannot blow the step up
 constexpr int kSgdSlots = 36;        // grad[32] | loss | weight | (34: unused) | curvature sum
 
+// The barrier between sgd_apply's phases: the whole block's (kWaveOnly false) or the calling wave's.
 template <bool kWaveOnly>
 __device__ __forceinline__ void sgd_sync() {
   if constexpr (kWaveOnly) nsync();
-  else sgd_sync<kWaveOnly>();
+  else __syncthreads();
 }
 
 // kWaveOnly: ONE wave calls it (t = its lane) and its phases are ordered by wave barriers only --
@@ -1552,8 +1575,10 @@ __device__ __forceinline__ void sgd_sync() {
 template <bool kWaveOnly>
 __device__ void sgd_apply(const double* rd, double* __restrict__ st, float* __restrict__ w32, int* __restrict__ done,
                           const double* __restrict__ aff, const SgdArgs& a, int t, bool mapped) {
-  // rd: the reduced [36] sums in LDS (raw row space).  Every thread of the block calls this (it
-  // holds block barriers); only the first wave (t < 64) reads or writes state.
+  // rd: the reduced [36] sums in LDS (raw row space; standardized space when `mapped`).  kWaveOnly
+  // false: EVERY thread of the block calls this from block-uniform control flow -- it holds block
+  // barriers, under conditions (aff, a.epoch_end) that are kernel arguments; only the first wave
+  // (t < 64) reads or writes state.
   __shared__ double rz[32], ss[kW + 32], cA[32], iA[32];
   if (aff) {
     if (t < 64) {
@@ -2421,6 +2446,10 @@ int sgd_full_blocks() {
     blocks = 2 * cus;
   }
   return blocks;
+}
+
+SgdConstants sgd_constants() {
+  return {kSgdReplicas, kSgdGroups, kSgdLoads, kPersistWaves, kPersistReplicas, (double)kSynQ, (double)kSynQL};
 }
 
 int sgd_persist_blocks(int grid_blocks) {

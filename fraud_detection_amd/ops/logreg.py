@@ -34,6 +34,9 @@ STATE_SIZE = 256
 # state offsets (logreg.hip)
 S_W, S_WPREV, S_STEP, S_VEL = 0, 32, 64, 96
 S_OBJPREV, S_ITER, S_BACKTRACKS, S_GMAX, S_OBJ, S_NACC, S_CONV = 128, 129, 130, 131, 132, 133, 134
+# SGD slots (logreg.hip kAvg .. kLr): Polyak sum, epoch gradient sum, epoch loss / weight, averaged
+# steps, the last step's clamped mean curvature and step size
+S_AVG, S_EPG, S_EPLOSS, S_EPW, S_NAVG, S_DBAR, S_LR = 160, 192, 224, 225, 226, 227, 228
 
 
 @dataclass
@@ -1050,12 +1053,7 @@ def sgd_fit(rows: torch.Tensor, C: float = 1.0, lr=SGD_LR, momentum: float = SGD
         # a fit that had converged before the checkpoint stays converged: its remaining passes and
         # updates are no-ops, as in the uninterrupted fit (reset() cleared the device flag)
         ws.done.fill_(int(float(got[0]["state"][S_CONV]) > 0))
-    v = virtual
-    mq, k = (v.nbr.shape if v is not None else (0, 1))
-
-    vargs = (ptr(v.parents) if v else 0, ptr(v.nbr) if v else 0, ptr(v.lam) if v else 0,
-             ptr(v.off) if v else 0, ptr(v.cnt) if v else 0, int(rows.shape[0]),
-             int(v.q_offset) if v else 0, int(mq), int(k), int(hole[0]), int(hole[1]))
+    vargs = _virtual_args(rows, virtual, hole)
 
     def run_steps(s0: int, s1: int, prepped: bool = False, export_slot: int | None = None) -> int:
         """Steps [s0, s1) of the schedule: ONE persistent launch (a grid barrier per step, the
@@ -1214,13 +1212,9 @@ def sgd_minibatch_sums(rows: torch.Tensor, w: torch.Tensor, nb: int, phase: int,
     """One SGD minibatch pass, reduced (test / diagnostic API): gradient, loss, weight and
     curvature sums of minibatch ``phase`` of ``nb`` at weights ``w`` on the device."""
     m = native()
+    rows, virtual, _, n = _sgd_once_inputs(rows, virtual, None)
     ws = LRWorkspace(rows.device)
     ws.reset(w.cpu().double().numpy(), class_w)
-    n = rows.shape[0]
-    if virtual is not None:
-        virtual.check(rows)
-        virtual.prepare()
-        n += virtual.n_new
     fp8 = storage_kind(rows) != "bf16"
     blocks = blocks or ref.sgd_grid_blocks(rows.shape[0], nb, ws.sgd_blocks)
     s = stream_of(rows)
@@ -1229,6 +1223,128 @@ def sgd_minibatch_sums(rows: torch.Tensor, w: torch.Tensor, nb: int, phase: int,
     red = ws.red[:SGD_SLOTS].cpu().numpy()
     return {"grad": red[:32].copy(), "loss": float(red[32]), "wsum": float(red[33]), "dsum": float(red[35]),
             "blocks": blocks}
+
+
+def _virtual_args(rows: torch.Tensor, v: VirtualSmote | None, hole: tuple = (0, 0)) -> tuple:
+    """The SmoteView and RowHole arguments of the SGD entry points (parents .. k, hole_at, hole_len)."""
+    mq, k = (v.nbr.shape if v is not None else (0, 1))
+    return (ptr(v.parents) if v else 0, ptr(v.nbr) if v else 0, ptr(v.lam) if v else 0, ptr(v.off) if v else 0,
+            ptr(v.cnt) if v else 0, int(rows.shape[0]), int(v.q_offset) if v else 0, int(mq), int(k),
+            int(hole[0]), int(hole[1]))
+
+
+def _sgd_once_inputs(rows, virtual, hole):
+    check_rows(rows)
+    rows, hole = _apply_hole(rows, hole)
+    if virtual is not None and virtual.n_new == 0:
+        virtual = None
+    if virtual is not None:
+        virtual.check(rows)
+        virtual.prepare()
+    end = rows.shape[0] + (virtual.n_new if virtual is not None else 0)  # physical end: the hole included
+    return rows, virtual, hole, end
+
+
+def sgd_pass_sums_once(rows: torch.Tensor, w32, rsub: int, phase: int, blocks: int, class_w=(1.0, 1.0),
+                       affine=None, virtual: VirtualSmote | None = None, hole: tuple | None = None, done: int = 0,
+                       fp8_scale: float = DEFAULT_FP8_SCALE, workspace: LRWorkspace | None = None) -> np.ndarray:
+    """ONE launch of the lean data-parallel pass (the FUSE pass kernels with ``sums``): minibatch
+    ``phase`` of ``rsub`` on a grid of ``blocks`` blocks at the fp32 weights ``w32`` ([32], read as
+    they are: no folding) -> the int64 [36] fixed-point sums (2^-20 units; mapped to standardized
+    space with ``affine``, [64] fp64 c | inv).  Test/diagnostic API; ops/reference.py sgd_pass_sums
+    is its oracle.  ``workspace``: its sgd_acc / sgd_sums are used as they are (not cleared: the pass
+    must leave the accumulators zero), so a caller can look at them afterwards; ``done``: the flag
+    before the launch (1: the pass must touch nothing)."""
+    rows, virtual, hole, end = _sgd_once_inputs(rows, virtual, hole)
+    ws = workspace or LRWorkspace(rows.device, 1)
+    ws.w32.copy_(torch.from_numpy(np.ascontiguousarray(w32, dtype=np.float32).reshape(NCOLS)))
+    ws.class_w.copy_(torch.tensor([float(class_w[0]), float(class_w[1])], dtype=torch.float32))
+    ws.done.fill_(int(done))
+    aff = None
+    if affine is not None:
+        aff = torch.from_numpy(np.ascontiguousarray(affine, dtype=np.float64).reshape(64)).to(rows.device)
+    native().sgd_pass_sums(ptr(rows), int(storage_kind(rows) != "bf16"), float(fp8_scale), end, ptr(ws.w32),
+                           ptr(ws.class_w), ptr(ws.done), int(rsub), int(phase), int(blocks),
+                           *_virtual_args(rows, virtual, hole), ptr(ws.sgd_acc), ptr(ws.sgd_acc[SGD_ACC_WORDS:]),
+                           ptr(ws.sgd_sums), ptr(aff) if aff is not None else 0, stream_of(rows))
+    return ws.sgd_sums.cpu().numpy()
+
+
+def _sgd_once_workspace(dev, state, w32, done, affine):
+    state = np.ascontiguousarray(state, dtype=np.float64).reshape(-1)
+    if state.shape[0] != STATE_SIZE:
+        raise ValueError("the SGD state is [256] float64")
+    ws = LRWorkspace(dev, 1)
+    ws.state.copy_(torch.from_numpy(state))
+    if w32 is not None:
+        ws.w32.copy_(torch.from_numpy(np.ascontiguousarray(w32, dtype=np.float32).reshape(NCOLS)))
+    ws.done.fill_(int(done))
+    aff = None
+    if affine is not None:
+        aff = torch.from_numpy(np.ascontiguousarray(affine, dtype=np.float64).reshape(64)).to(dev)
+    return ws, aff
+
+
+def _sgd_step_args(d, C, c, momentum, fit_intercept, nb, avg, epoch_end, tol) -> tuple:
+    return (int(d), float(C), float(c), float(momentum), int(fit_intercept), int(nb), int(avg), int(epoch_end),
+            float(tol))
+
+
+def sgd_update_once(kind: str, sums, state, d: int = 30, C: float = 1.0, c: float = 0.5, momentum: float = 0.5,
+                    fit_intercept: bool = True, nb: int = 1, avg: int = 0, epoch_end: int = 0, tol: float = 1e-3,
+                    affine=None, done: int = 0, w32=None, device=None):
+    """ONE launch of an SGD update kernel on given sums and state (test/diagnostic API;
+    ops/reference.py SgdStateRef is its mirror).  ``kind`` "red": sgd_update_kernel on [36] float64
+    raw sums (mapped by the kernel when ``affine`` is given); "fixed": sgd_update_fixed_kernel on
+    [36] int64 sums in 2^-20 units, already in standardized space.  ``state``: [256] float64 (the
+    S_* offsets).  Returns (state [256] float64, w32 [32] float32, done int)."""
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    ws, aff = _sgd_once_workspace(dev, state, w32, done, affine)
+    args = (ptr(ws.state), ptr(ws.w32), ptr(ws.done), ptr(aff) if aff is not None else 0,
+            *_sgd_step_args(d, C, c, momentum, fit_intercept, nb, avg, epoch_end, tol), stream_of(ws.state))
+    if kind == "red":
+        ws.red[:SGD_SLOTS].copy_(torch.from_numpy(np.ascontiguousarray(sums, dtype=np.float64).reshape(SGD_SLOTS)))
+        native().sgd_update(ptr(ws.red), *args)
+    elif kind == "fixed":
+        ws.sgd_sums.copy_(torch.from_numpy(np.ascontiguousarray(sums, dtype=np.int64).reshape(SGD_SLOTS)))
+        native().sgd_update_fixed(ptr(ws.sgd_sums), *args)
+    else:
+        raise ValueError("sgd_update_once: kind is 'red' or 'fixed'")
+    return ws.state.cpu().numpy(), ws.w32.cpu().numpy(), int(ws.done.cpu()[0])
+
+
+def sgd_step_once(partial, nblocks: int, state, d: int = 30, C: float = 1.0, c: float = 0.5, momentum: float = 0.5,
+                  fit_intercept: bool = True, nb: int = 1, avg: int = 0, epoch_end: int = 0, tol: float = 1e-3,
+                  affine=None, done: int = 0, w32=None, device=None):
+    """ONE launch of sgd_step_kernel (the fixed-order reduce of ``partial``, [nblocks, PART_STRIDE]
+    float32, and the update) on a given state; arguments and result as sgd_update_once."""
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    part = np.ascontiguousarray(partial, dtype=np.float32).reshape(int(nblocks), PART_STRIDE)
+    ws, aff = _sgd_once_workspace(dev, state, w32, done, affine)
+    pd = torch.from_numpy(part).to(dev)
+    native().sgd_step(ptr(pd), int(nblocks), ptr(ws.state), ptr(ws.w32), ptr(ws.done),
+                      ptr(aff) if aff is not None else 0,
+                      *_sgd_step_args(d, C, c, momentum, fit_intercept, nb, avg, epoch_end, tol), stream_of(ws.state))
+    return ws.state.cpu().numpy(), ws.w32.cpu().numpy(), int(ws.done.cpu()[0])
+
+
+def sgd_run_steps(rows: torch.Tensor, ws: LRWorkspace, s0: int, s1: int, blocks: int, nbs, lrs, subs=None,
+                  C: float = 1.0, momentum: float = SGD_MOMENTUM, tol: float = SGD_TOL, avg_from: int = 0,
+                  d: int = 30, fit_intercept: bool = True, affine: torch.Tensor | None = None,
+                  virtual: VirtualSmote | None = None, hole: tuple | None = None,
+                  fp8_scale: float = DEFAULT_FP8_SCALE):
+    """Steps [s0, s1) of a schedule (epoch e: nbs[e] minibatches at step scalar lrs[e], row
+    sub-sample subs[e]) as fused per-step launches on a prepared workspace -- ``ws.reset`` done by
+    the caller, the state, weights and done flag carried in ``ws`` from call to call.  Exactly what
+    sgd_fit(persistent=False) enqueues (test/diagnostic API)."""
+    rows, virtual, hole, end = _sgd_once_inputs(rows, virtual, hole)
+    epochs = len(nbs)
+    subs = [1] * epochs if subs is None else [int(x) for x in subs]
+    native().sgd_run(ptr(rows), int(storage_kind(rows) != "bf16"), float(fp8_scale), end, ptr(ws.w32), ptr(ws.class_w),
+                     ptr(ws.done), ptr(ws.partial), int(blocks), stream_of(rows), *_virtual_args(rows, virtual, hole),
+                     ptr(ws.state), ptr(affine) if affine is not None else 0, int(d), float(C), float(momentum),
+                     int(fit_intercept), float(tol), int(nbs[0]), epochs, int(avg_from), [float(x) for x in lrs],
+                     int(s0), int(s1), ptr(ws.sgd_acc), ptr(ws.sgd_acc[SGD_ACC_WORDS:]), subs, [int(x) for x in nbs])
 
 
 S_SGD_FAULT = 229  # logreg.hip kSgdFault: 2 = the persistent SGD fit ran on its recovery launch

@@ -401,9 +401,22 @@ def sgd_pick_batches(n_picks: int, nb: int, pick_tile: int = PICK_TILE_BF16) -> 
 SGD_DBAR_FLOOR = 1e-3
 
 
+def sgd_map_sums(g: np.ndarray, affine) -> np.ndarray:
+    """Gradient sums over pivot-shifted rows s, z = (s - c) inv, mapped to standardized space:
+    rz_t = inv_t (g_t - c_t g_bias) (logreg.hip wave_sums_fixed / sgd_apply; affine = c | inv)."""
+    g = np.asarray(g, dtype=np.float64)[:32]
+    a = np.asarray(affine, dtype=np.float64)
+    return a[32:] * (g - a[:32] * g[BIAS_COL])
+
+
 class SgdStateRef:
     """Mirror of logreg.hip sgd_apply (fp64): heavy-ball momentum SGD with the step normalised by
-    the minibatch's mean curvature, Polyak averaging, epoch-end convergence state."""
+    the minibatch's mean curvature, Polyak averaging, epoch-end convergence state.
+
+    ``dbar`` / ``lr``: the step's clamped mean curvature and step size (state slots 227 / 228).
+    ``mag``: per quantity, the sum of the absolute values of the terms of its expression in the last
+    step (magnitudes propagated through the chain: |a + b| is charged |a|'s own magnitude plus
+    |b|'s) -- the scale a rounding-error bound of another fp64 evaluation order is stated against."""
 
     def __init__(self, w0: np.ndarray):
         self.w = np.asarray(w0, dtype=np.float64).copy()
@@ -418,42 +431,131 @@ class SgdStateRef:
         self.obj = np.inf
         self.converged = False
         self.done = False
+        self.dbar = 0.0
+        self.lr = 0.0
+        self.mag = {}
 
-    def step(self, g_raw, loss, wsum, dsum, d, C, c, mom, nb, avg, epoch_end, tol, fit_intercept=True):
+    def step(self, g_raw, loss, wsum, dsum, d, C, c, mom, nb, avg, epoch_end, tol, fit_intercept=True,
+             affine=None, mapped=False):
+        """``affine`` (c | inv, [64]): the sums were taken over pivot-shifted rows.  ``mapped`` False:
+        ``g_raw`` holds the raw sums and is mapped to standardized space first (sgd_map_sums);
+        True: it is mapped already (the fused passes map every wave's sums)."""
         if self.done:
             return
+        g_raw = np.asarray(g_raw, dtype=np.float64)[:32]
+        m_raw = np.abs(g_raw)
+        if affine is not None and not mapped:
+            a = np.asarray(affine, dtype=np.float64)
+            m_raw = np.abs(a[32:]) * (np.abs(g_raw) + np.abs(a[:32] * g_raw[BIAS_COL]))
+            g_raw = sgd_map_sums(g_raw, a)
         S = wsum if wsum > 0 else 1.0
         reg = 1.0 / (C * S * nb)
-        lr = c / max(dsum / S, SGD_DBAR_FLOOR)
+        dbar = max(dsum / S, SGD_DBAR_FLOOR)
+        lr = c / dbar
         g = np.zeros(32)
         g[:d] = g_raw[:d] / S + reg * self.w[:d]
+        m_g = np.zeros(32)
+        m_g[:d] = m_raw[:d] / S + np.abs(reg * self.w[:d])
         if fit_intercept:
             g[BIAS_COL] = g_raw[BIAS_COL] / S
+            m_g[BIAS_COL] = m_raw[BIAS_COL] / S
+        m_v = np.abs(mom * self.v) + lr * m_g
+        m_w = np.abs(self.w) + m_v
+        mag = {"v": m_v, "w": m_w, "ep_g": np.abs(self.ep_g) + m_raw, "ep_loss": abs(self.ep_loss) + abs(loss),
+               "ep_w": abs(self.ep_w) + abs(wsum), "avg": np.abs(self.avg) + (m_w if avg else 0.0),
+               "dbar": abs(dbar), "lr": abs(lr)}
         self.v = mom * self.v - lr * g
         self.w = self.w + self.v
-        self.ep_g += np.asarray(g_raw[:32], dtype=np.float64)
+        self.ep_g += g_raw
         self.ep_loss += loss
         self.ep_w += wsum
         if avg:
             self.avg += self.w
             self.n_avg += 1
         self.iter += 1
+        self.dbar, self.lr = dbar, lr
         if epoch_end:
             Sw = self.ep_w if self.ep_w > 0 else 1.0
             if self.n_avg > 0:
                 self.w = self.avg / self.n_avg
+                mag["w"] = mag["avg"] / self.n_avg
             G = np.zeros(32)
             G[:d] = self.ep_g[:d] / Sw + self.w[:d] / (C * Sw)
+            m_G = np.zeros(32)
+            m_G[:d] = mag["ep_g"][:d] / Sw + mag["w"][:d] / (C * Sw)
             if fit_intercept:
                 G[BIAS_COL] = self.ep_g[BIAS_COL] / Sw
+                m_G[BIAS_COL] = mag["ep_g"][BIAS_COL] / Sw
             self.gmax = float(np.abs(G).max())
             self.obj = self.ep_loss / Sw + 0.5 * float(self.w[:d] @ self.w[:d]) / (C * Sw)
+            mag["gmax"] = float(m_G.max())
+            # w^2 moves by 2 |w| dw: charged |w| magnitude squared, without the 1/2
+            mag["obj"] = mag["ep_loss"] / Sw + float(mag["w"][:d] @ mag["w"][:d]) / (C * Sw)
             self.ep_g[:] = 0.0
             self.avg[:] = 0.0
             self.ep_loss = self.ep_w = 0.0
             self.n_avg = 0
             if self.gmax <= tol:
                 self.converged = self.done = True
+        self.mag = mag
+
+
+def _sgd_members(rows_f64, rsub: int, phase: int, virtual):
+    """Rows of minibatch ``phase`` of ``rsub``: the stored rows of the 64-row tiles t with
+    t mod rsub == phase, then the virtual samples whose pick tile satisfies the same."""
+    R = np.asarray(rows_f64, dtype=np.float64).reshape(-1, NCOLS)
+    rsub, phase = int(rsub), int(phase)
+    if rsub < 1 or not 0 <= phase < rsub:
+        raise ValueError("sgd_pass_sums: rsub >= 1 and 0 <= phase < rsub")
+    M = R[(np.arange(R.shape[0], dtype=np.int64) // ROW_TILE) % rsub == phase]
+    if virtual is not None:
+        samples, pick, n_picks = virtual
+        pick = np.asarray(pick).astype(np.int64)
+        if pick.size and not (0 <= pick.min() and pick.max() < int(n_picks)):
+            raise ValueError("sgd_pass_sums: pick outside [0, n_picks)")
+        V = np.asarray(samples, dtype=np.float64).reshape(-1, NCOLS)
+        M = np.concatenate([M, V[(pick // PICK_TILE) % rsub == phase]])
+    return M
+
+
+def _sgd_row_terms(M, w, class_w):
+    """(X, r, s, loss terms, curvature terms) of the rows M at weights w."""
+    y = M[:, LABEL_COL].copy()
+    X = M.copy()
+    X[:, LABEL_COL] = 0.0
+    w = np.asarray(w, dtype=np.float64).copy()
+    w[LABEL_COL] = 0.0
+    z = X @ w
+    with np.errstate(over="ignore"):
+        p = sigmoid(z)
+    s = np.where(y > 0.5, class_w[1], class_w[0])
+    return X, s * (p - y), s, s * (np.logaddexp(0.0, z) - y * z), s * p * (1 - p)
+
+
+def sgd_pass_sums(rows_f64, w, class_w, rsub: int, phase: int, virtual=None, affine=None) -> np.ndarray:
+    """float64 [36], the sums of one SGD minibatch pass (logreg.hip FISH passes): gradient [32] | loss
+    | weight | 0 | curvature sum s p (1 - p), over the stored rows with (row // 64) % rsub == phase
+    and, with ``virtual`` = (the samples' fp64 rows, every sample's pick, n_picks), the samples with
+    (pick // PICK_TILE) % rsub == phase.  A CV hole is applied by deleting the block from the rows
+    first.  ``affine`` (c | inv): the gradient mapped to standardized space (sgd_map_sums; the
+    device maps every wave's sums -- the map is linear, so mapping the total is the same)."""
+    X, r, s, lt, ct = _sgd_row_terms(_sgd_members(rows_f64, rsub, phase, virtual), w, class_w)
+    out = np.zeros(36)
+    out[:32] = X.T @ r
+    out[32], out[33], out[35] = lt.sum(), s.sum(), ct.sum()
+    if affine is not None:
+        out[:32] = sgd_map_sums(out[:32], affine)
+    return out
+
+
+def sgd_sums_abs(rows_f64, w, class_w, rsub: int, phase: int, virtual=None) -> np.ndarray:
+    """sgd_pass_sums (unmapped) over the absolute value of every term: sum |r_i x_it| per gradient
+    column, and the loss, weight and curvature sums themselves (their terms are not negative)."""
+    X, r, s, lt, ct = _sgd_row_terms(_sgd_members(rows_f64, rsub, phase, virtual), w, class_w)
+    out = np.zeros(36)
+    out[:32] = np.abs(X).T @ np.abs(r)
+    out[32], out[33], out[35] = np.abs(lt).sum(), np.abs(s).sum(), np.abs(ct).sum()
+    return out
 
 
 # ------------------------------------------------------------------------------------------
