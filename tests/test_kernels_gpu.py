@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 import torch
 
+import _smote_cases as SC
 from fraud_detection_amd.data.synthetic import separable
 from fraud_detection_amd.ops import knn as K
 from fraud_detection_amd.ops import logreg as L
@@ -429,6 +430,9 @@ def test_smote_generate_matches_oracle(dev):
     exp = ref.smote_generate(C, nbr.numpy(), 0, n_new, 42, 3)
     np.testing.assert_allclose(out.float().cpu().numpy(), exp, rtol=1e-2, atol=1e-2)
     assert np.all(out[:, 31].float().cpu().numpy() == 1.0)
+    # the single-rounded oracle (_smote_cases.py): the stored bf16 bits of every element
+    bits = SC.generate_oracle(C, nbr.numpy(), 0, SC.sample_ids(n_new), "bf16", seed=42, counter_base=3)
+    assert np.array_equal(out.view(torch.int16).cpu().numpy().view(np.uint16), bits)
 
 
 @pytest.mark.parametrize("link,tol", [("logit_model", 2e-4), ("identity", 2e-5), ("logit", 2e-4)])
@@ -586,6 +590,10 @@ def test_smote_affine_output_matches_oracle(dev):
     g, c = out_gpu.float().cpu(), out_cpu.float()
     assert torch.all((g - c).abs() <= 2.0 ** -7 * c.abs() + 1e-6)
     assert (g != c).float().mean().item() < 1e-3
+    # the single-rounded oracle (_smote_cases.py) applies the affine map as the kernel does: bit for bit
+    bits = SC.generate_oracle(xmin.numpy(), nbr.numpy(), 0, SC.sample_ids(50_000), "bf16", aff=st.aff.numpy(), seed=7,
+                              counter_base=0)
+    assert np.array_equal(out_gpu.view(torch.int16).cpu().numpy().view(np.uint16), bits)
 
 
 def test_newton_affine_matches_cpu(dev):

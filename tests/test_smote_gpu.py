@@ -1,15 +1,24 @@
 """SMOTE generation from bf16 parents in the training rows' space (ops/knn.smote_parents): the
 device parents equal the CPU ones bit for bit, and the generated rows match the numpy oracle
-(ops/reference.py smote_generate on the same parents) up to the oracle's two-rounding
-interpolation (one fma on the device)."""
+(ops/reference.py smote_generate on the same parents) up to that oracle's two-rounding
+interpolation (one fma on the device) -- and the single-rounded oracle of _smote_cases.py bit for bit."""
 import numpy as np
 import pytest
 import torch
 
+import _smote_cases as SC
 from fraud_detection_amd.data.synthetic import separable
 from fraud_detection_amd.ops import knn as K
 from fraud_detection_amd.ops import reference as ref
 from fraud_detection_amd.ops import scaler as S
+
+
+def _stored_bits(t: torch.Tensor) -> np.ndarray:
+    """Stored elements on the host: float32 bits (uint32), bf16 bits (uint16) or e4m3 codes (uint8)."""
+    if t.dtype == torch.uint8:
+        return t.cpu().numpy()
+    wide = t.dtype == torch.float32
+    return t.view(torch.int32 if wide else torch.int16).cpu().numpy().view(np.uint32 if wide else np.uint16)
 
 
 def _minority(n=60_000, seed=8):
@@ -95,6 +104,9 @@ def test_smote_generate_bf16_parents(dev, kind):
     else:
         np.testing.assert_allclose(got, exp, rtol=1e-6, atol=1e-6)
     assert np.all(got[:, 31] == 1.0) and np.all(got[:, 30] == 1.0)
+    # the single-rounded oracle (_smote_cases.py): the stored bits of every element, no allowance
+    bits = SC.generate_oracle(P.float().numpy(), nbr.numpy(), 0, SC.sample_ids(n_new), kind, seed=5, counter_base=1)
+    assert np.array_equal(_stored_bits(out_gpu), bits)
 
 
 def test_smote_bf16_parents_need_no_affine():
