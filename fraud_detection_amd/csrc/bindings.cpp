@@ -860,6 +860,15 @@ PYBIND11_MODULE(_fdx_native, m) {
                            P<const float>(tmax), mc_pad, mc, self_off, k, P<int>(oidx), P<float>(oscore),
                            P<int>(lists), P<int>(counts), P<float>(gmax), P<float>(thr), nsplit, S(s));
   });
+  m.def("knn3f_waves", [](int mq_pad, int mc_pad) { return fdx::knn3f_waves(mq_pad, mc_pad); });
+  m.attr("KNN3F_LIST_CAP") = fdx::knn3f_list_cap();
+  m.attr("KNN3F_MAX_WAVES") = fdx::knn3f_max_waves();
+  m.def("knn_topk3f", [](u Q, u Qhl, int mq_pad, int mq, u C, u Chl, u tmax, int mc_pad, int mc, int64_t self_off,
+                         int k, u oidx, u oscore, u scanned, int waves, int cap, u s) {
+    fdx::launch_knn_topk3f(P<const float>(Q), P<const void>(Qhl), mq_pad, mq, P<const float>(C), P<const void>(Chl),
+                           P<const float>(tmax), mc_pad, mc, self_off, k, P<int>(oidx), P<float>(oscore),
+                           P<uint8_t>(scanned), waves, cap, S(s));
+  });
   m.def("knn_topk", [](u Q, int mq_pad, int mq, u C, int mc_pad, int mc, int64_t self_off, int k, u oidx,
                        u oscore, u ws_score, u ws_idx, int nsplit, u s) {
     fdx::launch_knn_topk(P<const float>(Q), mq_pad, mq, P<const float>(C), mc_pad, mc,

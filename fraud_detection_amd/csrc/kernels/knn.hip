@@ -1158,6 +1158,259 @@ __global__ __launch_bounds__(256) void knn_rerank_sparse_kernel(const float* __r
   }
 }
 
+// ---- bf16x3f: the two passes, the threshold and the re-rank of bf16x3t in ONE launch -----------
+// Nothing bf16x3t hands from stage to stage has to leave the CU: a query block's threshold needs only
+// that block's group maxima, its re-rank only its own lists.  One workgroup of W waves owns the pair of
+// query blocks 2 x, 2 x + 1; wave y streams tile slice y (t_lo = tiles y / W) in both passes.
+//   phase 1: knn_groupmax_kernel's maxima in registers, then an LDS integer max per (block, group
+//     register, lane) on the order-preserving integer image of the float (a maximum is order-free;
+//     no score is -0, the accumulators start at +0) and on the bits of the slice's largest tile bound
+//     (>= 0; the margin is monotone in it, so the margin of the largest bound IS the largest margin);
+//   phase 2: every wave computes T and M of its lanes' queries with knn_threshold_kernel's arithmetic;
+//   phase 3: knn_filter_kernel's test and early outs; a survivor's index goes to its query's LDS list
+//     (one counter per query; past the cap counted, not stored);
+//   phase 4: 16 lanes per query re-score the listed candidates with knn_rerank_sparse_kernel's chain
+//     and merge; a query over the cap scans every candidate exactly.
+// The order (score, then index) is total, so neither W nor the order of the appends shows in the result.
+// Every wave reaches all three block barriers: nothing returns early, a wave with no tile (more waves
+// than tiles) or of the duplicate odd block only has nothing to contribute between them.
+// LDS: 8 KiB of maxima + 64 counters + 64 * cap list entries (dynamic).
+constexpr int kFusedMaxWaves = 12;  // 3 per SIMD: 168 VGPRs each (16 would leave 128 and spill)
+constexpr int kFusedListCap = 64;
+constexpr int kFusedMaxCap = 128;
+constexpr int kFusedLanes = 16;  // lanes per query in the re-rank
+
+__device__ __forceinline__ int knn_ord(float f) {  // order-preserving float -> int, its own inverse
+  const int b = __float_as_int(f);
+  return b ^ ((b >> 31) & 0x7fffffff);
+}
+__device__ __forceinline__ float knn_unord(int i) { return __int_as_float(i ^ ((i >> 31) & 0x7fffffff)); }
+
+// The lane index read afresh (v_mbcnt), opaque to the compiler: what depends only on it (row
+// addresses, the self candidates' registers) is then computed where it is used, not ahead of phase 1
+// and carried through the phase's tile loop, which alone fills the 168 registers of a 12-wave
+// workgroup: carried values went to scratch.
+__device__ __forceinline__ int knn_lane_again() {
+  int lane;
+  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
+  return lane;
+}
+
+template <int K>
+__global__ __launch_bounds__(kFusedMaxWaves* kWave) void knn_twopass_fused_kernel(
+    const float* __restrict__ Q, const uint4* __restrict__ Qhl, const float* __restrict__ C,
+    const uint4* __restrict__ Chl, const float* __restrict__ tmax, int qblocks, int mq, int mc_pad, int mc,
+    int64_t self_offset, int cap, int* __restrict__ out_idx, float* __restrict__ out_score,
+    uint8_t* __restrict__ scanned) {
+  __shared__ int s_max[2 * 16 * kWave];  // [block][register][lane], knn_ord of the maxima
+  __shared__ int s_cnt[2 * 32];          // [block][query]
+  __shared__ int s_tmm;
+  extern __shared__ int s_list[];        // [block][query][cap] candidate indices
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), W = blockDim.x >> 6;
+  const int b0 = 2 * blockIdx.x;
+  const bool has1 = b0 + 1 < qblocks;  // block-uniform
+  const int b1 = has1 ? b0 + 1 : b0;
+  for (int i = threadIdx.x; i < 2 * 16 * kWave; i += blockDim.x) s_max[i] = knn_ord(kNegBig);
+  if (threadIdx.x < 2 * 32) s_cnt[threadIdx.x] = 0;
+  if (threadIdx.x == 0) s_tmm = 0;
+  __syncthreads();
+  const int all_tiles = mc_pad / 32;
+  const int t_lo = (int)(((int64_t)all_tiles * wave) / W);
+  const int t_hi = (int)(((int64_t)all_tiles * (wave + 1)) / W);
+  KnnQFrag qa, qb;
+  // ---- phase 1: group maxima (knn_groupmax_kernel) ----
+  {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int h = lane >> 5, j = lane & 31;
+    qa = knn_load_qfrag(Qhl, b0 * 32 + j, h);
+    qb = knn_load_qfrag(Qhl, b1 * 32 + j, h);
+    const int ts = self_offset >= 0 ? (int)((self_offset + b0 * 32) >> 5) : -4;
+    const int sr0 = self_offset >= 0 ? (int)((self_offset + b0 * 32) & 31) : -64;  // + j: the lane's self row
+    const int d1 = b1 - b0;
+    float m0[16], m1[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) m0[r] = m1[r] = kNegBig;
+    float tmm = 0.0f;
+    auto take = [&](float (&m)[16], const f32x16_t& acc, int dt) {
+      if (dt == 0 || dt == 1) {  // wave-uniform: the self candidate stays out of the maxima
+        const int ln = knn_lane_again();
+        const int rs = sr0 + (ln & 31) - 32 * dt - 4 * (ln >> 5);  // register (r & 3) + 8 (r >> 2) of half h
+#pragma unroll
+        for (int r = 0; r < 16; ++r) m[r] = knn_max(m[r], (r & 3) + 8 * (r >> 2) == rs ? kNegBig : acc[r]);
+      } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) m[r] = knn_max(m[r], acc[r]);
+      }
+    };
+    knn_stream_tiles(qa, qb, Chl, tmax, lane, t_lo, t_hi,
+                     [&](int t, const f32x16_t& acc0, const f32x16_t& acc1, float tm) {
+                       tmm = fmaxf(tmm, tm);
+                       take(m0, acc0, t - ts);
+                       take(m1, acc1, t - ts - d1);
+                     });
+    const int ln = knn_lane_again();
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      atomicMax(&s_max[r * kWave + ln], knn_ord(m0[r]));
+      atomicMax(&s_max[(16 + r) * kWave + ln], knn_ord(m1[r]));
+    }
+    if (ln == 0) atomicMax(&s_tmm, __float_as_int(tmm));
+  }
+  __syncthreads();
+  // ---- phase 2: T and M of this lane's two queries (knn_threshold_kernel) ----
+  const int lane = knn_lane_again();
+  const int h = lane >> 5, j = lane & 31;
+  const int qg0 = b0 * 32 + j, qg1 = b1 * 32 + j;
+  const float tmm_all = __int_as_float(s_tmm);
+  const float qn0 = knn_query_norm(Q, qg0, h), qn1 = knn_query_norm(Q, qg1, h);
+  auto threshold = [&](int blk, float qn, bool real, float& T, float& M) {
+    float bs[K];  // this half's K largest group maxima, descending
+#pragma unroll
+    for (int k = 0; k < K; ++k) bs[k] = kNegBig;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      float x = knn_unord(s_max[(blk * 16 + r) * kWave + lane]);
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        const float hi = fmaxf(bs[k], x);
+        x = fminf(bs[k], x);
+        bs[k] = hi;
+      }
+    }
+    float ps[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) ps[k] = __shfl_xor(bs[k], 32, kWave);
+    int ia = 0, ib = 0;
+    float kth = kNegBig;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      float a = kNegBig, b = kNegBig;
+#pragma unroll
+      for (int u = 0; u < K; ++u) { if (u == ia) a = bs[u]; if (u == ib) b = ps[u]; }
+      const bool ta = a >= b;
+      kth = ta ? a : b;
+      ia += ta ? 1 : 0;
+      ib += ta ? 0 : 1;
+    }
+    kth = __shfl(kth, j, kWave);  // the value knn_threshold_kernel stores: half 0's
+    M = kMarginScale * fmaf(qn, tmm_all, 0.5f * tmm_all * tmm_all);
+    T = real ? kth - M : __builtin_inff();  // a padding query, and the duplicate block, list nothing
+  };
+  float T0, M0, T1, M1;
+  threshold(0, qn0, qg0 < mq, T0, M0);
+  threshold(1, qn1, has1 && qg1 < mq, T1, M1);
+  // ---- phase 3: the filter (knn_filter_kernel), survivors to the queries' LDS lists ----
+  {
+    const int64_t self0 = self_offset >= 0 ? self_offset + qg0 : -1, self1 = self_offset >= 0 ? self_offset + qg1 : -1;
+    auto filter = [&](int t, const f32x16_t& acc, float tm, float qn, float T, int64_t self_c, int qi) {
+      const float mg = kMarginScale * fmaf(qn, tm, 0.5f * tm * tm);
+      const float cut = T - mg;  // upper bound approx + mg >= T
+      float m4[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        m4[q] = knn_max(knn_max(acc[4 * q], acc[4 * q + 1]), knn_max(acc[4 * q + 2], acc[4 * q + 3]));
+      const float mx = knn_max(knn_max(m4[0], m4[1]), knn_max(m4[2], m4[3]));
+      if (!__any(mx >= cut)) return;
+      const int cbase = t * 32 + 4 * h;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        if (!__any(m4[q] >= cut)) continue;
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+          const int ci = cbase + rr + 8 * q;
+          if (acc[4 * q + rr] >= cut && ci != self_c && ci < mc) {
+            const int pos = atomicAdd(&s_cnt[qi], 1);
+            if (pos < cap) s_list[qi * cap + pos] = ci;  // past the cap: counted only (exact scan below)
+          }
+        }
+      }
+    };
+    knn_stream_tiles(qa, qb, Chl, tmax, lane, t_lo, t_hi,
+                     [&](int t, const f32x16_t& acc0, const f32x16_t& acc1, float tm) {
+                       filter(t, acc0, tm, qn0, T0, self0, j);
+                       filter(t, acc1, tm, qn1, T1, self1, 32 + j);
+                     });
+  }
+  __syncthreads();
+  // ---- phase 4: exact re-rank (knn_rerank_sparse_kernel), kFusedLanes lanes per query ----
+  constexpr int kQPW = kWave / kFusedLanes;  // queries a wave re-ranks at a time
+  for (int g = wave; g < 2 * 32 / kQPW; g += W) {  // wave-uniform trip count
+    const int qi = g * kQPW + lane / kFusedLanes, l = lane & (kFusedLanes - 1);
+    const int q = (b0 + (qi >> 5)) * 32 + (qi & 31);
+    const bool live = (qi < 32 || has1) && q < mq;
+    const int qq = live ? q : 0;
+    const int64_t self_c = self_offset >= 0 ? self_offset + qq : -1;
+    const float4* qp = reinterpret_cast<const float4*>(Q + (int64_t)qq * kCols);
+    auto exact = [&](int ci) -> float {  // knn_rerank_kernel's re-score: columns 0..31 in order
+      const float4* c = reinterpret_cast<const float4*>(C + (int64_t)ci * kCols);
+      float acc = 0.0f;
+#pragma unroll
+      for (int k = 0; k < kCols / 4; ++k) {
+        const float4 v = c[k], w = qp[k];
+        acc = fmaf(w.x, v.x, acc);
+        acc = fmaf(w.y, v.y, acc);
+        acc = fmaf(w.z, v.z, acc);
+        acc = fmaf(w.w, v.w, acc);
+      }
+      return acc;
+    };
+    float bs[K];
+    int bi[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) { bs[k] = kNegBig; bi[k] = 0x7fffffff; }
+    const int n = s_cnt[qi];
+    const bool over = live && n > cap;  // the same on all lanes of the query
+    if (live && !over) {
+      for (int e = l; e < n; e += kFusedLanes) {
+        const int ci = s_list[qi * cap + e];
+        topk_insert<K>(bs, bi, exact(ci), ci);
+      }
+    }
+    if (over) {  // the list overflowed: exact scan of every candidate
+      for (int ci = l; ci < mc; ci += kFusedLanes)
+        if (ci != self_c) topk_insert<K>(bs, bi, exact(ci), ci);
+    }
+#pragma unroll
+    for (int off = 1; off < kFusedLanes; off <<= 1) {  // knn_rerank_kernel's butterfly merge
+      float os[K];
+      int oi[K];
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        os[k] = __shfl_xor(bs[k], off, kWave);
+        oi[k] = __shfl_xor(bi[k], off, kWave);
+      }
+      float ns[K];
+      int ni[K];
+      int ia = 0, ib = 0;
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        float a = kNegBig, b = kNegBig;
+        int ai = 0x7fffffff, bj = 0x7fffffff;
+#pragma unroll
+        for (int u = 0; u < K; ++u) {
+          if (u == ia) { a = bs[u]; ai = bi[u]; }
+          if (u == ib) { b = os[u]; bj = oi[u]; }
+        }
+        const bool ta = !better(b, bj, a, ai);
+        ns[k] = ta ? a : b;
+        ni[k] = ta ? ai : bj;
+        ia += ta ? 1 : 0;
+        ib += ta ? 0 : 1;
+      }
+#pragma unroll
+      for (int k = 0; k < K; ++k) { bs[k] = ns[k]; bi[k] = ni[k]; }
+    }
+    if (live && l == 0) {
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        out_idx[(int64_t)q * K + k] = bi[k];
+        if (out_score) out_score[(int64_t)q * K + k] = bs[k];
+      }
+      if (scanned) scanned[q] = over ? 1 : 0;
+    }
+  }
+}
+
 // Merge the per-slice top-k lists of every query (same ordering: score desc, index asc).
 // lps (a power of two >= nsplit, <= 64) lanes per query: lane s loads slice s's sorted list, then
 // log2(lps) butterfly rounds merge lists pairwise through shuffles (a static-index merge of two
@@ -1375,6 +1628,55 @@ void launch_knn_topk3t(const float* Q, const void* Qhl, int mq_pad, int mq, cons
                                                              counts, out_idx, out_score);
   });
   check_launch("knn_topk3t");
+}
+
+int knn3f_list_cap() { return kFusedListCap; }
+int knn3f_max_waves() { return kFusedMaxWaves; }
+
+int knn3f_waves(int mq_pad, int mc_pad) {
+  // The waves of ONE workgroup share a CU, so W is bounded by what a CU holds of this kernel (the
+  // occupancy query below: registers and LDS: 12) and by the tiles (>= 8 each, as knn3t_splits).
+  // Of those, 8 = two per SIMD: alone the 13.6k self-search is fastest with 12 (0.108 ms the whole
+  // call against 0.115 with 8, 0.118 with 10: lab_sweep.json), but 12 waves of 164 VGPRs need an
+  // EMPTY CU, and in the fit the SMOTE bucket sort runs beside the search and its waves sit on
+  // every CU: the trace has the 12-wave kernel at 125 us there against ~90 alone.  Two waves per
+  // SIMD leave a third of the register file to the neighbour.  The plain bench, alternating, three
+  // runs each (waves_in_bench.jsonl): medians 0.858 / 0.858 / 0.864 ms per step with 8, 0.873 /
+  // 0.876 / 0.872 with 12, 0.879 / 0.879 / 0.874 with 10, the parent's 0.892 / 0.887 / 0.891
+  // (profiles/pr5_knn_fused).
+  static const int fit = [] {
+    for (int w = kFusedMaxWaves; w > 1; --w) {
+      int occ = 0;
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, knn_twopass_fused_kernel<5>, w * kWave,
+                                                       (size_t)2 * 32 * kFusedListCap * sizeof(int)) == hipSuccess &&
+          occ >= 1)
+        return w;
+    }
+    return 1;
+  }();
+  (void)mq_pad;
+  const int tiles = mc_pad / 32;
+  int w = fit < 8 ? fit : 8;
+  if (w > tiles / 8) w = tiles / 8;
+  if (w < 1) w = 1;
+  return w;
+}
+
+void launch_knn_topk3f(const float* Q, const void* Qhl, int mq_pad, int mq, const float* C, const void* Chl,
+                       const float* tmax, int mc_pad, int mc, int64_t self_offset, int k, int* out_idx,
+                       float* out_score, uint8_t* scanned, int waves, int cap, hipStream_t stream) {
+  if (mq_pad % 32 != 0 || mc_pad % 32 != 0) throw std::runtime_error("knn_topk3f: pads must be x32");
+  if (mq > mq_pad || mc > mc_pad || waves < 1 || waves > kFusedMaxWaves || cap < 1 || cap > kFusedMaxCap)
+    throw std::runtime_error("knn_topk3f: bad shapes, waves not in [1, 12] or list cap not in [1, 128]");
+  const int qblocks = mq_pad / 32;
+  const uint4* qh = reinterpret_cast<const uint4*>(Qhl);
+  const uint4* chl = reinterpret_cast<const uint4*>(Chl);
+  with_k(k, "knn_topk3f", [&](auto kk) {
+    constexpr int K = decltype(kk)::value;
+    knn_twopass_fused_kernel<K><<<(qblocks + 1) / 2, waves * kWave, (size_t)2 * 32 * cap * sizeof(int), stream>>>(
+        Q, qh, C, chl, tmax, qblocks, mq, mc_pad, mc, self_offset, cap, out_idx, out_score, scanned);
+  });
+  check_launch("knn_topk3f");
 }
 
 void launch_knn_topk(const float* Q, int mq_pad, int mq, const float* C,

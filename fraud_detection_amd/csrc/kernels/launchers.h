@@ -353,6 +353,17 @@ void launch_knn_topk3t(const float* Q, const void* Qhl, int mq_pad, int mq, cons
                        const float* tmax, int mc_pad, int mc, int64_t self_offset, int k, int* out_idx,
                        float* out_score, int* lists, int* counts, float* gmax, float* thr, int nsplit,
                        hipStream_t stream);
+// bf16x3f: launch_knn_topk3t's four stages in one launch, with no workspace: a workgroup of `waves`
+// waves (1 .. knn3f_max_waves()) owns a pair of query blocks and keeps the group maxima, the
+// threshold and the per-query candidate lists (`cap` entries, 1 .. 128) in LDS.  idx / score are
+// bf16x3t's bit for bit, whatever waves and cap.  scanned [mq] (nullable): 1 where the query's list
+// passed the cap and the exact scan answered it
+int knn3f_list_cap();
+int knn3f_max_waves();
+int knn3f_waves(int mq_pad, int mc_pad);
+void launch_knn_topk3f(const float* Q, const void* Qhl, int mq_pad, int mq, const float* C, const void* Chl,
+                       const float* tmax, int mc_pad, int mc, int64_t self_offset, int k, int* out_idx,
+                       float* out_score, uint8_t* scanned, int waves, int cap, hipStream_t stream);
 // the fp32 engine; nsplit > 1: per-slice lists in ws_score / ws_idx [nsplit][mq][k], then merged
 void launch_knn_topk(const float* Q, int mq_pad, int mq, const float* C,
                      int mc_pad, int mc, int64_t self_offset, int k, int* out_idx,

@@ -49,7 +49,18 @@ def _padded(X: torch.Tensor, n_pad: int) -> torch.Tensor:
 #           DP=8 global-scope rank it LOSES, 0.58 against 0.49 ms: there both passes stream the
 #           candidates at ~45 % of the MFMA rate and the second pass costs more than bf16x3r's list
 #           bookkeeping.
-# FDX_KNN (or engine=) selects one of the three.
+#   bf16x3f bf16x3t in ONE launch: a workgroup of W waves owns a pair of query blocks, wave y streams
+#           tile slice y in both passes, and the group maxima, the threshold and the per-query lists
+#           stay in LDS (no gmax / thr / lists / counts workspace); 16 lanes per query re-score the
+#           listed candidates -- knn.hip knn_twopass_fused_kernel.  idx and score are bf16x3t's bit for
+#           bit for every W.  nsplit= means W (at most KNN3F_MAX_WAVES: more is clamped, the result
+#           does not depend on it).  bf16x3t stays as the staged form the stage tests read.
+#           auto: where bf16x3t was picked (KNN_TWOPASS_ENGINE).  profiles/pr5_knn_fused: the lab's
+#           DP=1 self-search 0.104 ms against bf16x3t's 0.126 and bf16x3r's 0.161 (whole call); the plain
+#           bench's step, alternating with the parent, medians 0.873 / 0.869 / 0.861 ms against 0.893 /
+#           0.900 / 0.895.  At the DP=8 rank it is bf16x3t's 0.58 ms against bf16x3r's 0.49: auto keeps
+#           bf16x3r there.
+# FDX_KNN (or engine=) selects one of the four.
 # Retired, each measured slower than what replaced it: fp32lds (LDS-staged candidate chunks shared by
 # 4-wave workgroups) and bf16x3 (the filter with an exact re-score inside the tile loop), 0.66-0.99x
 # and 0.86-0.96x of fp32 from 13.6k to 170k rows (profiles/r2_s3i), bf16x3 superseded by bf16x3r
@@ -59,6 +70,8 @@ def _padded(X: torch.Tensor, n_pad: int) -> torch.Tensor:
 KNN_BF16X3_MIN_CANDIDATES = 1 << 13
 KNN_TWOPASS_MAX_CANDIDATES = 1 << 14
 KNN_TWOPASS_MIN_QUERIES = 1 << 12
+KNN_TWOPASS_ENGINE = "bf16x3f"  # what auto runs in the two-pass range: bf16x3t or its one-launch form
+KNN_ENGINES = ("fp32", "bf16x3r", "bf16x3t", "bf16x3f")
 
 
 def knn_engine(mq: int, mc: int, engine: str | None = None) -> str:
@@ -66,8 +79,8 @@ def knn_engine(mq: int, mc: int, engine: str | None = None) -> str:
     if e == "auto":
         if mc < KNN_BF16X3_MIN_CANDIDATES:
             return "fp32"
-        return "bf16x3t" if mc <= KNN_TWOPASS_MAX_CANDIDATES and mq >= KNN_TWOPASS_MIN_QUERIES else "bf16x3r"
-    if e not in ("fp32", "bf16x3r", "bf16x3t"):
+        return KNN_TWOPASS_ENGINE if mc <= KNN_TWOPASS_MAX_CANDIDATES and mq >= KNN_TWOPASS_MIN_QUERIES else "bf16x3r"
+    if e not in KNN_ENGINES:
         raise ValueError(f"unknown k-NN engine {e!r}")
     return e
 
@@ -88,15 +101,17 @@ def _check_parents(parents: torch.Tensor | None, C: torch.Tensor, affine: torch.
 def knn_topk(Q: torch.Tensor, C: torch.Tensor, k: int = 5, self_offset: int = -1, want_dist: bool = False,
              nsplit: int | None = None, engine: str | None = None, parents: torch.Tensor | None = None,
              parents_affine: torch.Tensor | None = None, _diag: dict | None = None, raw_stats=None,
-             _operands: dict | None = None):
+             _operands: dict | None = None, list_cap: int | None = None):
     """k nearest candidates (squared L2 over the 30 feature columns) of each query row.
 
     Q [mq, 32] / C [mc, 32] fp32 padded rows (columns 30/31, intercept and label, are ignored).  If ``self_offset >= 0``, query row q is candidate
     row ``self_offset + q`` and is excluded (SMOTE's self-match removal).  Returns int32 [mq, k]
     (ascending distance, ties -> smaller index) and optionally squared distances.
-    ``nsplit``: candidate slices searched by separate workgroups and merged (None = auto).
+    ``nsplit``: candidate slices searched by separate workgroups and merged (None = auto); for
+    "bf16x3f" the waves W of a workgroup, each with its own slice.  ``list_cap`` ("bf16x3f" only): LDS
+    list entries per query (None = KNN3F_LIST_CAP).
     ``engine``: "fp32" = exact fp32 MFMA chain over every candidate (16 x 32x32x2 f32 per tile);
-    "bf16x3r" / "bf16x3t" = a hi.hi + hi.lo + lo.hi bf16 MFMA filter (6 x 32x32x16 bf16 per tile)
+    "bf16x3r" / "bf16x3t" / "bf16x3f" = a hi.hi + hi.lo + lo.hi bf16 MFMA filter (6 x 32x32x16 bf16 per tile)
     with a provable margin, the survivors listed under a running or a fixed threshold and re-scored
     exactly in fp32 by a second kernel (see the engine notes above); None/"auto" (FDX_KNN env) picks
     by size.  All return the exact fp32 ranking.
@@ -135,7 +150,9 @@ def knn_topk(Q: torch.Tensor, C: torch.Tensor, k: int = 5, self_offset: int = -1
     m = native()
     s = stream_of(Q)
     eng = knn_engine(mq, mc, engine)
-    bf16 = eng != "fp32"  # bf16x3r / bf16x3t: the filter streams hi/lo bf16 candidate tiles
+    if list_cap is not None and eng != "bf16x3f":
+        raise ValueError("list_cap is bf16x3f's")
+    bf16 = eng != "fp32"  # bf16x3r / bf16x3t / bf16x3f: the filter streams hi/lo bf16 candidate tiles
     mq_pad, mc_pad = _pad32(mq), _pad32(mc)
     Qc, Cc = Q.contiguous(), C.contiguous()
     # GEMM-ready rows: the -0.5||c||^2 term rides in column 30 (see knn.hip knn_prep_kernel)
@@ -176,7 +193,8 @@ def knn_topk(Q: torch.Tensor, C: torch.Tensor, k: int = 5, self_offset: int = -1
     if nsplit is not None:
         ns = max(1, int(nsplit))
     else:
-        ns = {"fp32": m.knn_splits, "bf16x3r": m.knn3r_splits, "bf16x3t": m.knn3t_splits}[eng](mq_pad, mc_pad)
+        ns = {"fp32": m.knn_splits, "bf16x3r": m.knn3r_splits, "bf16x3t": m.knn3t_splits,
+              "bf16x3f": m.knn3f_waves}[eng](mq_pad, mc_pad)
     if eng == "fp32":
         ws_s = ws_i = None
         if ns > 1:  # the slices' lists, merged by a second kernel
@@ -184,6 +202,14 @@ def knn_topk(Q: torch.Tensor, C: torch.Tensor, k: int = 5, self_offset: int = -1
             ws_i = torch.empty((ns, mq, k), device=Q.device, dtype=torch.int32)
         m.knn_topk(ptr(Qp), mq_pad, mq, ptr(Cp), mc_pad, mc, int(self_offset), int(k), ptr(idx),
                    ptr(score), ptr(ws_s), ptr(ws_i), ns, s)
+    elif eng == "bf16x3f":
+        ns = min(ns, int(m.KNN3F_MAX_WAVES))
+        cap = int(m.KNN3F_LIST_CAP) if list_cap is None else int(list_cap)
+        scanned = torch.empty(mq, device=Q.device, dtype=torch.uint8) if _diag is not None else None
+        m.knn_topk3f(ptr(Qp), ptr(Qhl), mq_pad, mq, ptr(Cp), ptr(Chl), ptr(tmax), mc_pad, mc, int(self_offset),
+                     int(k), ptr(idx), ptr(score), ptr(scanned), ns, cap, s)
+        if _diag is not None:  # which queries took the exact scan (diagnostics; synchronises)
+            _diag.update(nsplit=ns, list_cap=cap, exact_scans=int(scanned.sum()), scanned=scanned.bool())
     else:
         qb = mq_pad // 32
         nb = ns * qb * 64

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """k-NN (SMOTE minority self-search, k=5) engine scaling on one GPU: the exact fp32 MFMA chain vs
-the two bf16x3 collect engines (running and fixed threshold, exact re-rank), from the 10M-row
+the bf16x3 collect engines (running threshold, fixed threshold, fixed threshold in one launch; exact
+re-rank), from the 10M-row
 bench's 13.6k minority rows up to the 170k of a 100M-row table (BASELINE config 5).  Minority rows of the separable generator, standardized.
 
     python tools/knn_bench.py [--sizes 13600,54400,170000] [--reps 5]
@@ -34,7 +35,7 @@ def main():
         C[:, 30] = 1.0
         res = {"minority_rows": int(C.shape[0]), "k": 5}
         ref = None
-        for eng in ("fp32", "bf16x3r", "bf16x3t"):
+        for eng in ("fp32", "bf16x3r", "bf16x3t", "bf16x3f"):
             f = lambda: K.knn_topk(C, C, 5, 0, engine=eng)  # noqa: E731
             out = f()
             torch.cuda.synchronize()
@@ -51,6 +52,7 @@ def main():
                 res[f"{eng}_lists_equal_frac"] = round((out == ref).all(1).float().mean().item(), 6)
         res["speedup_bf16x3r"] = round(res["fp32_ms"] / res["bf16x3r_ms"], 2)
         res["speedup_bf16x3t"] = round(res["fp32_ms"] / res["bf16x3t_ms"], 2)
+        res["speedup_bf16x3f"] = round(res["fp32_ms"] / res["bf16x3f_ms"], 2)
         print(json.dumps(res), flush=True)
         del X, y, xm, C
         torch.cuda.empty_cache()

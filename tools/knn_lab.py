@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
 """k-NN (SMOTE self-search, k=5) at the bench shapes: engines x candidate slices.
 
-    python tools/knn_lab.py [--reps 20] [--engines fp32,bf16x3r,bf16x3t] [--json out.json]
+    python tools/knn_lab.py [--reps 20] [--engines fp32,bf16x3r,bf16x3t,bf16x3f] [--json out.json]
 
 Shapes: DP1 (the 10M-row bench's 13.6k minority rows against themselves) and the DP=8 global-scope
 rank (its 13.6k minority rows against all 8 ranks' 108.8k).  For every nsplit the event-timed
 median of the whole knn_topk call (prep + search + merge) and whether the lists equal the
-auto-split lists exactly.  (r4: a pilot search seeding every slice's threshold was measured here
+auto-split lists exactly.  For bf16x3f nsplit is the waves of a workgroup (clamped to the launcher's
+limit) and --caps sweeps its LDS list cap per query.  (r4: a pilot search seeding every slice's threshold was measured here
 too, 1-3% slower at every split count -- profiles/r4_g/knn_lab.json -- and removed.)
 """
 import argparse
@@ -26,6 +27,7 @@ def main():
     ap.add_argument("--json", default=None)
     ap.add_argument("--splits", default="1,2,4,8,16,32")
     ap.add_argument("--engines", default="fp32")
+    ap.add_argument("--caps", default="", help="bf16x3f: list caps to time at the auto wave count, e.g. 16,32,64,128")
     ap.add_argument("--alternate", default=None, metavar="ENG[:NSPLIT],...",
                     help="also time these engines one call each in turn, --reps rounds (medians per engine)")
     a = ap.parse_args()
@@ -56,14 +58,17 @@ def main():
         torch.cuda.synchronize()
         return float(np.median([ev[i].elapsed_time(ev[i + 1]) for i in range(a.reps)]))
 
-    splitter = {"fp32": "knn_splits", "bf16x3r": "knn3r_splits", "bf16x3t": "knn3t_splits"}
+    splitter = {"fp32": "knn_splits", "bf16x3r": "knn3r_splits", "bf16x3t": "knn3t_splits", "bf16x3f": "knn3f_waves"}
     for name, (Q, Cc, off) in shapes.items():
         mq, mc = Q.shape[0], Cc.shape[0]
         ref = K.knn_topk(Q, Cc, 5, off, engine="fp32")
         for eng in a.engines.split(","):
             auto = getattr(native(), splitter[eng])((mq + 31) // 32 * 32, (mc + 31) // 32 * 32)
             rec = {"engine": eng, "mq": mq, "mc": mc, "auto_nsplit": int(auto), "cases": []}
-            for ns in sorted({int(v) for v in a.splits.split(",")} | {int(auto)}):
+            splits = {int(v) for v in a.splits.split(",")} | {int(auto)}
+            if eng == "bf16x3f":
+                splits = {min(v, int(native().KNN3F_MAX_WAVES)) for v in splits}
+            for ns in sorted(splits):
                 f = lambda: K.knn_topk(Q, Cc, 5, off, engine=eng, nsplit=ns)  # noqa: E731
                 got = f()
                 ms = timed(f)
@@ -79,6 +84,16 @@ def main():
                         "lists_equal": bool((got == ref).all().item())}
                 rec["cases"].append(case)
                 print(json.dumps({name: case}), flush=True)
+            if eng == "bf16x3f":
+                for cap in (int(v) for v in a.caps.split(",") if v):
+                    f = lambda: K.knn_topk(Q, Cc, 5, off, engine=eng, nsplit=int(auto), list_cap=cap)  # noqa: E731
+                    got = f()
+                    dg = {}
+                    K.knn_topk(Q, Cc, 5, off, engine=eng, nsplit=int(auto), list_cap=cap, _diag=dg)
+                    case = {"engine": eng, "nsplit": int(auto), "list_cap": cap, "ms": round(timed(f), 4),
+                            "exact_scans": dg["exact_scans"], "lists_equal": bool((got == ref).all().item())}
+                    rec.setdefault("caps", []).append(case)
+                    print(json.dumps({name: case}), flush=True)
             best = min(rec["cases"], key=lambda c: c["ms"])
             base = [c for c in rec["cases"] if c["nsplit"] == auto][0]
             rec["best"], rec["auto"] = best, base
