@@ -907,6 +907,19 @@ PYBIND11_MODULE(_fdx_native, m) {
                          T, depth, base, P<const uint32_t>(bw), bw_ld, n_bg, f0, P<float>(phi), P<float>(fx),
                          P<float>(f0o), S(s));
   });
+  m.def("treeshap_path", [](u Xs, int ldx, int E, int d, u feat, u thr, u leaf, u frac, u dleft, int T, int depth,
+                            float base, float f0, u phi, u fx, u f0o, u s) {
+    fdx::launch_treeshap_path(P<const float>(Xs), ldx, E, d, P<const int>(feat), P<const float>(thr),
+                              P<const float>(leaf), P<const float>(frac), P<const uint8_t>(dleft), T, depth, base, f0,
+                              P<float>(phi), P<float>(fx), P<float>(f0o), S(s));
+  });
+  m.def("treeshap_path_trees_in_lds", &fdx::treeshap_path_trees_in_lds);
+  m.def("tree_cover", [](u X, int64_t n, int ld, int d, u feat, u thr, u leaf, u dleft, int T, int depth, float base,
+                         int kind, u ws, u cover, u s) {
+    fdx::launch_tree_cover(P<const float>(X), n, ld, d, P<const int>(feat), P<const float>(thr), P<const float>(leaf),
+                           P<const uint8_t>(dleft), T, depth, base, kind, P<float>(ws), P<int64_t>(cover), S(s));
+  });
+  m.def("tree_cover_chunk_trees", &fdx::tree_cover_chunk_trees);
   m.def("kernelshap_tree", [](u Xs, int ldx, int E, int d, u feat, u thr, u leaf, int T, int depth, float base, u bw,
                               int bw_ld, int nbg, u Zm, int nS, int S_pad, int parts, u A, u Az, int link, u phi,
                               u fx, u f0, u ws, u cnt, u s) {

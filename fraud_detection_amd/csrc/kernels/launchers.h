@@ -435,6 +435,22 @@ int kernelshap_linear_resident(int S_pad, int parts);
 void launch_treeshap(const float* Xs, int ldx, int n_expl, int d, const int* feat, const float* thr,
                      const float* leaf, int ntrees, int depth, float base_margin, const uint32_t* bw, int bw_ld,
                      int n_bg, float f0, float* phi, float* fx_out, float* f0_out, hipStream_t stream);
+// path-dependent TreeSHAP (treeshap_path.hip): exact SHAP of the ensemble margin from the model's
+// node covers, no background; frac [T][2^(depth+1)] fp32 child fractions cover[k] / cover[parent]
+// by heap node, dleft u8 [T][2^depth - 1] or null, f0 = base margin + sum_t v_t(empty set)
+void launch_treeshap_path(const float* Xs, int ldx, int n_expl, int d, const int* feat, const float* thr,
+                          const float* leaf, const float* frac, const uint8_t* dleft, int ntrees, int depth,
+                          float base_margin, float f0, float* phi, float* fx_out, float* f0_out,
+                          hipStream_t stream);
+// whether launch_treeshap_path keeps leaves, split features and fractions in LDS for this shape
+bool treeshap_path_trees_in_lds(int d, int ntrees, int depth);
+// node covers (treecover.hip): cover int64 [ntrees][2^(depth+1)] by heap node over the rows X;
+// kind 0 = row counts, 1 = sums of llrint(p (1 - p) 2^30).  margin_ws: fp32 [n] scratch, needed by
+// kind 1 when ntrees exceeds tree_cover_chunk_trees(depth) (null otherwise)
+void launch_tree_cover(const float* X, int64_t n, int ld, int d, const int* feat, const float* thr,
+                       const float* leaf, const uint8_t* dleft, int ntrees, int depth, float base_margin,
+                       int kind, float* margin_ws, int64_t* cover, hipStream_t stream);
+int tree_cover_chunk_trees(int depth);  // trees per launch: the LDS chunk
 void launch_kernelshap_tree(const float* Xs, int ldx, int n_expl, int d, const int* feat, const float* thr,
                             const float* leaf, int ntrees, int depth, float base_margin, const uint32_t* bw,
                             int bw_ld, int n_bg, const uint32_t* Zm, int S, int S_pad, int parts,

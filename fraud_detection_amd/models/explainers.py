@@ -29,10 +29,13 @@ XGBoost model):
     through the ensemble inside the kernel (kernelshap_tree_kernel), never materialised;
   * ``TreeExplainer`` -- interventional TreeSHAP of the GBDT margin: exact, no coalition sampling
     (treeshap.hip), orders of magnitude less work than KernelSHAP on trees;
+  * ``TreePathExplainer`` -- path-dependent TreeSHAP of the GBDT margin from the node covers stored
+    in the model (treeshap_path.hip): exact, no background, NaN follows the learned default
+    direction -- xgboost's pred_contribs;
   * ``FunctionKernelExplainer`` -- any callable on device tensors (e.g. a torch model): masked rows
     are built in chunks on the device, the model is called on them, and the shared WLS operator
     projects the coalition values.
-All three share one cached coalition design per (M, nsamples, seed).
+The KernelSHAP paths share one cached coalition design per (M, nsamples, seed).
 """
 from __future__ import annotations
 
@@ -501,6 +504,157 @@ class TreeExplainer:
 
             return treeshap(torch.from_numpy(X).to(self.device), self)
         return treeshap_reference(_standardize(X, self.mean, self.scale), self.Bs, self.ens)
+
+
+def path_fractions(ens) -> np.ndarray:
+    """float64 [T, 2^(D+1)]: frac[t, k] = cover[t, k] / cover[t, k >> 1] for heap node k >= 2, the
+    weight of child k when its parent's feature is absent.  A split node of cover 0 weighs its
+    children 1/2 and 1/2 (the game stays total; the shap package would give NaN); a pass-through
+    node sends everything left (1 and 0).  Slots 0 and 1 are 1."""
+    if ens.cover is None:
+        raise ValueError("the ensemble stores no node cover: run node_cover first")
+    T, ni = ens.feat.shape
+    cover = np.asarray(ens.cover, np.float64)
+    frac = np.ones((T, 2 * (ni + 1)))
+    for k in range(2, 2 * (ni + 1)):
+        par = k >> 1
+        cp = cover[:, par]
+        split = ens.feat[:, par - 1] >= 0
+        ratio = np.divide(cover[:, k], cp, out=np.full(T, 0.5), where=cp > 0)
+        frac[:, k] = np.where(split, ratio, 1.0 if k % 2 == 0 else 0.0)
+    return frac
+
+
+def path_direction_bits(Xs: np.ndarray, ens) -> np.ndarray:
+    """tree_direction_bits with NaN routed by default_left (gbdt_predict's walk)."""
+    Xs = np.asarray(Xs, np.float32)
+    T, ni = ens.feat.shape
+    dl = ens.default_left if getattr(ens, "default_left", None) is not None else np.zeros((T, ni), np.uint8)
+    out = np.zeros((T, Xs.shape[0]), np.uint32)
+    for n in range(ni):
+        f = ens.feat[:, n]
+        v = Xs[:, np.maximum(f, 0)].T                       # [T, n]
+        right = (f[:, None] >= 0) & ~(v < ens.thr[:, n][:, None]) & ~(np.isnan(v) & (dl[:, n][:, None] != 0))
+        out |= right.astype(np.uint32) << np.uint32(n + 1)
+    return out
+
+
+def path_expected_value(ens, frac: np.ndarray | None = None) -> float:
+    """f0 = base_margin + sum_t v_t(empty set): every leaf weighted by the product of its path's
+    fractions, in fp64."""
+    frac = path_fractions(ens) if frac is None else frac
+    D = ens.depth
+    w = np.ones((ens.n_trees, 1 << D))
+    for l in range(1 << D):
+        heap = (1 << D) + l
+        for j in range(D):
+            w[:, l] *= frac[:, heap >> (D - j - 1)]
+    return float(ens.base_margin + (w * ens.leaf.astype(np.float64)).sum())
+
+
+def treeshap_path_reference(Xs: np.ndarray, ens) -> tuple:
+    """fp64 per-leaf oracle of path-dependent TreeSHAP on STANDARDIZED rows (treeshap_path.hip's
+    game; a NaN follows default_left): for leaf L with value v and the distinct split features M
+    on its path, z_j = the product of the path's edge fractions at the nodes splitting on j and
+    o_j = 1 iff x goes the path's way at all of them; for i in M
+        phi_i += v (o_i - z_i) sum_{S in M \\ {i}} |S|! (m - |S| - 1)! / m! prod_{j in S} o_j prod_{j not in S + i} z_j.
+    Returns (phi [E, d] of the margin, margin(x) [E], f0 = base margin + sum_t v_t(empty set))."""
+    Xs = np.asarray(Xs, np.float32)
+    frac = path_fractions(ens)
+    xw = path_direction_bits(Xs, ens)
+    D = ens.depth
+    E, d = Xs.shape
+    phi = np.zeros((E, d))
+    fact = [math.factorial(i) for i in range(D + 1)]
+    feat = ens.feat.tolist()
+    for t in range(ens.n_trees):
+        for l in range(1 << D):
+            heap = (1 << D) + l
+            path, dead = [], False                       # (node, child) pairs at split nodes
+            for j in range(D):
+                k, c = heap >> (D - j), heap >> (D - j - 1)
+                if feat[t][k - 1] < 0:
+                    dead = dead or bool(c & 1)
+                else:
+                    path.append((k, c))
+            if dead or not path:
+                continue
+            v = float(ens.leaf[t, l])
+            M = sorted({feat[t][k - 1] for k, _ in path})
+            m = len(M)
+            for e in range(E):
+                xb = int(xw[t, e])
+                z = {f: 1.0 for f in M}
+                o = {f: 1.0 for f in M}
+                for k, c in path:
+                    f = feat[t][k - 1]
+                    z[f] *= frac[t, c]
+                    if ((xb >> k) & 1) != (c & 1):
+                        o[f] = 0.0
+                for i in M:
+                    rest = [f for f in M if f != i]
+                    W = 0.0
+                    for s in range(m):
+                        for S in itertools.combinations(rest, s):
+                            term = fact[s] * fact[m - s - 1] / fact[m]
+                            for f in rest:
+                                term *= o[f] if f in S else z[f]
+                            W += term
+                    phi[e, i] += v * (o[i] - z[i]) * W
+    fx = _margins_from_bits(xw, ens).astype(np.float64)
+    return phi, fx, path_expected_value(ens, frac)
+
+
+class TreePathExplainer:
+    """Path-dependent TreeSHAP of a tree ensemble (ops/gbdt.TreeEnsemble on standardized rows) over
+    RAW inputs, in margin (log-odds) space -- xgboost's predict(pred_contribs=True) and
+    shap.TreeExplainer(model) without data: exact, and with no background set.  The node covers
+    stored in the model (ops/gbdt.node_cover) weigh the branches of an absent feature, and a NaN
+    in x follows the node's learned default direction, so ensembles with default_left are
+    accepted (csrc/kernels/treeshap_path.hip).  At most 30 columns, depth <= 5, <= 2048 trees."""
+
+    link = "logit_model"
+
+    def __init__(self, ens, mean, scale, device="auto"):
+        if getattr(ens, "cover", None) is None:
+            raise ValueError("TreePathExplainer needs the model's node covers: compute them with node_cover "
+                             "(GBDTClassifier.compute_cover, fit(..., record_cover=True) or train --gbdt-cover)")
+        if not 1 <= ens.depth <= 5:
+            raise ValueError("path TreeSHAP supports depth 1..5 (the reference trains max_depth=5)")
+        if not 1 <= ens.n_trees <= 2048:
+            raise ValueError("path TreeSHAP supports 1..2048 trees")
+        self.mean = np.asarray(mean, np.float64)
+        self.scale = np.asarray(scale, np.float64)
+        self.d = len(self.mean)
+        _check_tree_features(ens, self.d)
+        if np.asarray(ens.cover).shape != (ens.n_trees, 2 << ens.depth):
+            raise ValueError(f"cover must be [{ens.n_trees}, {2 << ens.depth}]")
+        if not np.all(np.isfinite(ens.cover)) or np.any(np.asarray(ens.cover) < 0):
+            raise ValueError("node covers must be finite and >= 0")
+        self.ens = ens
+        self.frac = path_fractions(ens)                      # fp64; the device gets it rounded once
+        self.f0 = path_expected_value(ens, self.frac)
+        self.device = torch.device("cuda", 0) if (device == "auto" and torch.cuda.is_available()) else torch.device(
+            "cpu" if device == "auto" else device)
+        self._dev_cache = None
+
+    @property
+    def expected_value(self) -> float:
+        return self.f0
+
+    def shap_values(self, X) -> np.ndarray:
+        return self.explain(X)[0]
+
+    def explain(self, X):
+        """-> (phi [E, d], margin(x) [E], f0) in log-odds space; sum(phi) = margin(x) - f0."""
+        X = np.ascontiguousarray(X, np.float32)
+        if self.device.type == "cuda":
+            from ..ops.treeshap import treeshap_path
+
+            return treeshap_path(torch.from_numpy(X).to(self.device), self)
+        if X.shape[0] == 0:
+            return np.zeros((0, self.d)), np.zeros(0), self.f0
+        return treeshap_path_reference(_standardize(X, self.mean, self.scale), self.ens)
 
 
 class FunctionKernelExplainer:

@@ -105,6 +105,7 @@ class GBDTClassifier:
     def __getstate__(self):  # joblib/pickle: plain values and host arrays only (no device tensors)
         st = dict(self.__dict__)
         st["_dens"] = None
+        st.pop("_pexpl", None)
         st["params"] = dict(self.params.__dict__)
         return st
 
@@ -117,7 +118,7 @@ class GBDTClassifier:
         self.__dict__.update(st)
 
     def fit(self, X, y, sample_weight=None, comm=None, eval_set=None, verbose: bool = False,
-            sample_weight_eval_set=None):
+            sample_weight_eval_set=None, record_cover: bool = False):
         """``eval_set``: ``[(Xv, yv)]`` (exactly one set, xgboost's list form) evaluated after every
         round with the constructor's ``eval_metric`` (a name or a list of "logloss", "error", "auc",
         "aucpr"; default "logloss"; "aucpr" is sklearn's average precision over tie groups, which
@@ -133,7 +134,18 @@ class GBDTClassifier:
         "logloss" and "error" become weighted means, "auc" / "aucpr" with evaluation weights raise
         NotImplementedError.  ``None`` everywhere is the unweighted call.  Out of scope: the quantile
         cuts stay unweighted, and GBDTPipeline, DeviceGBDTCV and the train entry point take no
-        weights (SMOTE's synthetic rows have no defined weight; imblearn drops weights too)."""
+        weights (SMOTE's synthetic rows have no defined weight; imblearn drops weights too).
+
+        ``record_cover=True``: after the last round, store xgboost's per-node sum_hess of the training
+        rows in the model (``compute_cover(X)``; unweighted, this process's rows) so
+        ``predict_contribs`` works without another call.  The default enqueues exactly the launches
+        it always did."""
+        self._fit(X, y, sample_weight, comm, eval_set, verbose, sample_weight_eval_set)
+        if record_cover:
+            self.compute_cover(X)
+        return self
+
+    def _fit(self, X, y, sample_weight, comm, eval_set, verbose, sample_weight_eval_set):
         dev = self._dev(X)
         Xt = _as_tensor(X, dev)
         yt = (y if isinstance(y, torch.Tensor) else torch.from_numpy(np.asarray(y))).to(dev).to(torch.uint8)
@@ -210,6 +222,52 @@ class GBDTClassifier:
 
     def predict(self, X, iteration_range=None) -> np.ndarray:
         return (self.predict_margin(X, iteration_range) > 0.0).astype(np.int64)
+
+    def compute_cover(self, X, kind: str = "hessian") -> "GBDTClassifier":
+        """Store the node covers of the fitted trees over the rows X in the model (ops/gbdt.node_cover):
+        ``kind="hessian"`` is xgboost's sum_hess, ``"count"`` the rows per node.  They are what
+        ``predict_contribs`` and the "cover" importances read, and ``save_model`` writes them."""
+        self._check()
+        dev = self._dev(X)
+        Xt = _as_tensor(X, dev)
+        if Xt.is_cuda and (self._dens is None or self._dens.device != Xt.device):
+            self._dens = gb.DeviceEnsemble(self.ensemble, Xt.device)
+        q = gb.node_cover(Xt, self.ensemble, kind, self._dens).cpu().numpy()
+        self.ensemble = self.ensemble.with_cover(q, kind)
+        if self._dens is not None:
+            self._dens.ens = self.ensemble
+        self._pexpl = None
+        return self
+
+    def predict_contribs(self, X, iteration_range=None) -> np.ndarray:
+        """xgboost's ``predict(pred_contribs=True)``: float64 [n, d + 1] path-dependent TreeSHAP values
+        of the margin from the stored node covers, the last column the bias f0; every row sums to
+        ``predict_margin``.  A NaN follows the learned default direction.  ``iteration_range=(0, k)``
+        uses the first k trees and their covers.  Needs ``compute_cover`` (or
+        ``fit(..., record_cover=True)``) first."""
+        self._check()
+        if self.ensemble.cover is None:
+            raise ValueError("predict_contribs needs node covers: call compute_cover(X) (ops/gbdt.node_cover) or "
+                             "fit(..., record_cover=True) first")
+        from .explainers import TreePathExplainer
+
+        k = self._n_trees(iteration_range)
+        k = self.ensemble.n_trees if k is None else k
+        dev = self._dev(X)
+        cache = getattr(self, "_pexpl", None)
+        key = (k, str(dev), id(self.ensemble))
+        if cache is None or cache[0] != key:
+            d = self.ensemble.n_features
+            cache = (key, TreePathExplainer(self.ensemble.head(k), np.zeros(d), np.ones(d), device=str(dev)))
+            self._pexpl = cache
+        Xh = X.detach().cpu().numpy() if isinstance(X, torch.Tensor) else np.asarray(X)
+        phi, _, f0 = cache[1].explain(np.ascontiguousarray(Xh, np.float32))
+        return np.concatenate([phi, np.full((phi.shape[0], 1), f0)], 1)
+
+    def feature_importance(self, kind: str = "gain") -> np.ndarray:
+        """``TreeEnsemble.feature_importance``: "gain", "weight", "total_gain", "cover", "total_cover"."""
+        self._check()
+        return self.ensemble.feature_importance(kind)
 
     @property
     def feature_importances_(self) -> np.ndarray:

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import os
 import warnings
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 
 import numpy as np
 import torch
@@ -239,10 +239,35 @@ class TreeEnsemble:
     base_score: float = 0.5
     params: dict = field(default_factory=dict)
     default_left: np.ndarray | None = None  # [T, 2^D - 1] uint8: a NaN goes left at the node; None: all zero
+    # [T, 2^(D+1)] float64 node covers by 1-based heap node (index 0 unused), node_cover's int64 sums
+    # divided by 2^30 for cover_kind "hessian" (xgboost's sum_hess), the row counts themselves for
+    # "count"; None: the model stores no cover (path-dependent TreeSHAP needs one)
+    cover: np.ndarray | None = None
+    cover_kind: str | None = None
 
     @property
     def has_default_left(self) -> bool:
         return self.default_left is not None and bool(np.any(self.default_left))
+
+    def with_cover(self, q: np.ndarray, kind: str) -> "TreeEnsemble":
+        """A copy of this ensemble that stores node_cover's int64 table ``q`` of ``kind``."""
+        q = np.asarray(q)
+        if q.shape != (self.n_trees, 2 << self.depth):
+            raise ValueError(f"cover must be [{self.n_trees}, {2 << self.depth}], got {q.shape}")
+        if kind not in R.COVER_KINDS:
+            raise ValueError(f"cover kind must be one of {R.COVER_KINDS}, not {kind!r}")
+        cover = q.astype(np.float64) / (R.COVER_SCALE if kind == "hessian" else 1.0)
+        return replace(self, cover=cover, cover_kind=kind)
+
+    def head(self, k: int) -> "TreeEnsemble":
+        """The first k trees (and their covers)."""
+        if not 1 <= k <= self.n_trees:
+            raise ValueError(f"tree count must be in [1, {self.n_trees}]")
+        if k == self.n_trees:
+            return self
+        cut = lambda a: None if a is None else a[:k]  # noqa: E731
+        return replace(self, feat=self.feat[:k], bin=self.bin[:k], thr=self.thr[:k], gain=self.gain[:k],
+                       leaf=self.leaf[:k], default_left=cut(self.default_left), cover=cut(self.cover))
 
     @property
     def n_trees(self) -> int:
@@ -257,15 +282,27 @@ class TreeEnsemble:
         return float(np.log(self.base_score / (1.0 - self.base_score)))
 
     def feature_importance(self, kind: str = "gain") -> np.ndarray:
-        """xgboost-style importances: "gain" (mean gain per split) or "weight" (split count)."""
+        """xgboost-style importances: "gain" (mean gain per split), "weight" (split count),
+        "total_gain", and from the stored node covers "cover" (mean cover per split) and
+        "total_cover"."""
+        if kind not in ("gain", "weight", "total_gain", "cover", "total_cover"):
+            raise ValueError(f"unknown importance kind {kind!r}")
         d = self.n_features
         cnt = np.zeros(d)
         tot = np.zeros(d)
         m = self.feat >= 0
         np.add.at(cnt, self.feat[m], 1.0)
-        np.add.at(tot, self.feat[m], self.gain[m])
+        if kind in ("cover", "total_cover"):
+            if self.cover is None:
+                raise ValueError(f'importance kind "{kind}" needs node covers: run node_cover '
+                                 "(GBDTClassifier.compute_cover, or fit(..., record_cover=True)) first")
+            np.add.at(tot, self.feat[m], self.cover[:, 1: self.feat.shape[1] + 1][m])
+        else:
+            np.add.at(tot, self.feat[m], self.gain[m])
         if kind == "weight":
             return cnt
+        if kind in ("total_gain", "total_cover"):
+            return tot
         return np.where(cnt > 0, tot / np.maximum(cnt, 1), 0.0)
 
     def to_dict(self) -> dict:
@@ -277,6 +314,9 @@ class TreeEnsemble:
              "nbins": self.nbins.tolist()}
         if self.has_default_left:  # an ensemble without a default-left node serialises as it always did
             o["default_left"] = np.asarray(self.default_left, np.uint8).tolist()
+        if self.cover is not None:  # likewise: a model without cover writes the file it always wrote
+            o["cover"] = np.asarray(self.cover, np.float64).tolist()
+            o["cover_kind"] = self.cover_kind
         return o
 
     @classmethod
@@ -297,7 +337,10 @@ class TreeEnsemble:
                    leaf=np.asarray(o["leaf"], np.float32).reshape(-1, 1 << depth), cuts=cuts, nbins=nbins,
                    base_score=float(o["base_score"]), params=dict(o.get("params", {})),
                    default_left=(np.asarray(o["default_left"], np.uint8).reshape(-1, ni)
-                                 if o.get("default_left") is not None else None))
+                                 if o.get("default_left") is not None else None),
+                   cover=(np.asarray(o["cover"], np.float64).reshape(-1, 2 << depth)
+                          if o.get("cover") is not None else None),
+                   cover_kind=o.get("cover_kind") if o.get("cover") is not None else None)
 
 
 # Device-side split words (csrc/kernels/gbdt.hip goes_right): a default-left split of bin b (b = -1:
@@ -1268,3 +1311,43 @@ def predict_margin(X: torch.Tensor, ens: TreeEnsemble, dens: DeviceEnsemble | No
 def predict_proba(X: torch.Tensor, ens: TreeEnsemble, dens: DeviceEnsemble | None = None,
                   n_trees: int | None = None) -> torch.Tensor:
     return torch.sigmoid(predict_margin(X, ens, dens, n_trees))
+
+
+# ---- node covers -----------------------------------------------------------------------------
+def tree_cover_chunk(depth: int) -> int:
+    """Trees whose nodes and int64 leaf sums one tree_cover launch keeps in LDS (the launcher's
+    chunk): (32768 - 1024) // ((2 (2^D - 1) + 2^D) 4 + 2^D 8)."""
+    return int(native().tree_cover_chunk_trees(int(depth)))
+
+
+def node_cover(X: torch.Tensor, ens: TreeEnsemble, kind: str = "hessian",
+               dens: DeviceEnsemble | None = None) -> torch.Tensor:
+    """int64 [T, 2^(D+1)] node covers of ``ens`` over the standardized rows X [n, d] (fp32, d <= 30,
+    any row stride), by 1-based heap node; reference_gbdt.node_cover has the definitions.  Device
+    rows run csrc/kernels/treecover.hip, CPU rows the numpy oracle.  ``TreeEnsemble.with_cover``
+    stores the result in a model.  The sums are integers, so per-rank tables of a data-parallel
+    run would simply add; that all-reduce is not wired up."""
+    if kind not in R.COVER_KINDS:
+        raise ValueError(f"cover kind must be one of {R.COVER_KINDS}, not {kind!r}")
+    n, d = X.shape
+    if d != ens.n_features:
+        raise ValueError(f"model has {ens.n_features} features, X has {d}")
+    if int(ens.feat.max(initial=-1)) >= d or int(ens.feat.min(initial=0)) < -1:
+        raise ValueError("the ensemble's split features do not fit the rows' width")
+    dl = ens.default_left if ens.has_default_left else None
+    if not X.is_cuda:
+        return torch.from_numpy(R.node_cover(X.numpy(), ens.feat, ens.thr, ens.leaf, ens.depth, ens.base_margin, dl,
+                                             kind))
+    if X.dtype != torch.float32 or X.stride(1) != 1:
+        raise ValueError("X must be float32 with unit column stride")
+    if not 1 <= ens.depth <= 8:
+        raise ValueError("node_cover supports depth 1..8")
+    dens = dens if dens is not None and dens.device == X.device else DeviceEnsemble(ens, X.device)
+    out = torch.empty((ens.n_trees, 2 << ens.depth), dtype=torch.int64, device=X.device)
+    need_ws = kind == "hessian" and ens.n_trees > tree_cover_chunk(ens.depth) and n > 0
+    ws = torch.empty(n, dtype=torch.float32, device=X.device) if need_ws else None
+    native().tree_cover(ptr(X) if n else 0, n, X.stride(0) if n else d, d, ptr(dens.feat), ptr(dens.thr),
+                        ptr(dens.leaf), ptr(dens.dleft) if getattr(dens, "dleft", None) is not None else 0,
+                        ens.n_trees, ens.depth, float(ens.base_margin), 1 if kind == "hessian" else 0,
+                        ptr(ws) if ws is not None else 0, ptr(out), stream_of(X))
+    return out

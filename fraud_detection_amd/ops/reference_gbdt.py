@@ -730,3 +730,48 @@ def predict_margin_bins(bins: np.ndarray, feat: np.ndarray, binv: np.ndarray, le
             node = 2 * node + 1 + right
         out = (out + leaf[t][node - ((1 << depth) - 1)]).astype(np.float32)
     return out
+
+
+COVER_SCALE = float(2 ** 30)  # fixed point of a row's hessian in node covers
+COVER_KINDS = ("hessian", "count")
+
+
+def node_cover(X: np.ndarray, feat: np.ndarray, thr: np.ndarray, leaf: np.ndarray, depth: int,
+               base_margin: float = 0.0, default_left: np.ndarray | None = None, kind: str = "hessian") -> np.ndarray:
+    """int64 [T, 2^(depth+1)] node covers by 1-based heap node (index 0 unused and 0) over the fp32
+    rows X [n, d]: the oracle of csrc/kernels/treecover.hip.
+
+    kind "count": rows that reach the node.  kind "hessian" (xgboost's sum_hess): the sum over those
+    rows of h_q = llrint(p (1 - p) 2^30), p = sigmoid((double)m), m the fp32 margin of the row before
+    tree t (float(base_margin) plus the leaves of trees 0 .. t-1 added in tree order in fp32:
+    predict_margin(..., n_trees = t)).  Routing is predict_margin's.  Leaves are accumulated and an
+    internal node is the exact integer sum of its children."""
+    if kind not in COVER_KINDS:
+        raise ValueError(f"cover kind must be one of {COVER_KINDS}, not {kind!r}")
+    X = np.asarray(X, dtype=np.float32)
+    n = X.shape[0]
+    T = feat.shape[0]
+    ni, nl = (1 << depth) - 1, 1 << depth
+    out = np.zeros((T, 2 * nl), np.int64)
+    rows = np.arange(n)
+    margin = np.full(n, np.float32(base_margin), dtype=np.float32)
+    for t in range(T):
+        node = np.zeros(n, np.int64)
+        for _ in range(depth):
+            f = feat[t][node]
+            xv = X[rows, np.maximum(f, 0)]
+            right = (f >= 0) & ~(xv < thr[t][node])
+            if default_left is not None:
+                right &= ~(np.isnan(xv) & (default_left[t][node] != 0))
+            node = 2 * node + 1 + right
+        lf = node - ni
+        if kind == "count":
+            w = np.ones(n, np.int64)
+        else:
+            p = 1.0 / (1.0 + np.exp(-margin.astype(np.float64)))
+            w = np.rint(p * (1.0 - p) * COVER_SCALE).astype(np.int64)
+        np.add.at(out[t], nl + lf, w)
+        margin = (margin + leaf[t][lf]).astype(np.float32)
+        for k in range(nl - 1, 0, -1):
+            out[t, k] = out[t, 2 * k] + out[t, 2 * k + 1]
+    return out

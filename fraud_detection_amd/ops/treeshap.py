@@ -27,6 +27,59 @@ def _device_design(expl, dev):
     return t
 
 
+def _device_path_design(expl, dev):
+    key = ("path", str(dev))
+    if expl._dev_cache is not None and expl._dev_cache[0] == key:
+        return expl._dev_cache[1]
+    from .scaler import stats_from_numpy
+
+    ens = expl.ens
+    dl = ens.default_left if getattr(ens, "has_default_left", False) else None
+    t = {
+        "feat": torch.from_numpy(np.ascontiguousarray(ens.feat, np.int32)).to(dev),
+        "thr": torch.from_numpy(np.ascontiguousarray(ens.thr, np.float32)).to(dev),
+        "leaf": torch.from_numpy(np.ascontiguousarray(ens.leaf, np.float32)).to(dev),
+        "frac": torch.from_numpy(np.ascontiguousarray(expl.frac, np.float32)).to(dev),  # fp64 rounded once
+        "dleft": torch.from_numpy(np.ascontiguousarray(dl, np.uint8)).to(dev) if dl is not None else None,
+        "stats": stats_from_numpy(expl.mean, expl.scale, device=dev),
+    }
+    expl._dev_cache = (key, t)
+    return t
+
+
+def treeshap_path_lds_resident(d: int, n_trees: int, depth: int) -> bool:
+    """Whether launch_treeshap_path keeps leaves, split features and fractions in LDS."""
+    return bool(native().treeshap_path_trees_in_lds(int(d), int(n_trees), int(depth)))
+
+
+def treeshap_path(X: torch.Tensor, expl, sync: bool = True, out=None):
+    """Path-dependent TreeSHAP (csrc/kernels/treeshap_path.hip).  X [E, d] RAW fp32 on device
+    (standardized on device with the model's scaler; a NaN stays NaN and follows default_left)
+    -> (phi [E, d], margin(x) [E], f0): phi sums to margin(x) - f0, f0 = the explainer's expected
+    value.  Numpy if ``sync`` else device tensors (``out``: preallocated (phi, fx, f0) device
+    tensors).  E = 0 launches nothing and returns empty results of these shapes."""
+    _check_x(X, expl.d)
+    m = native()
+    dev = X.device
+    t = _device_path_design(expl, dev)
+    from .scaler import scale_cast
+
+    E = X.shape[0]
+    phi, fx, f0 = _outputs(E, expl.d, dev, out)
+    ens = expl.ens
+    if E == 0:
+        if not sync:
+            return phi, fx, f0
+        return np.zeros((0, expl.d)), np.zeros(0), float(expl.f0)
+    Xs = scale_cast(X, t["stats"], out_dtype="f32")  # [E, 32]
+    m.treeshap_path(ptr(Xs), Xs.stride(0), E, expl.d, ptr(t["feat"]), ptr(t["thr"]), ptr(t["leaf"]), ptr(t["frac"]),
+                    ptr(t["dleft"]), ens.n_trees, ens.depth, float(ens.base_margin), float(expl.f0), ptr(phi),
+                    ptr(fx), ptr(f0), stream_of(X))
+    if not sync:
+        return phi, fx, f0
+    return phi.cpu().numpy().astype(np.float64), fx.cpu().numpy().astype(np.float64), float(expl.f0)
+
+
 def treeshap(X: torch.Tensor, expl, sync: bool = True, out=None):
     """X [E, d] RAW fp32 on device (standardized on device with the model's scaler) -> (phi [E, d],
     margin(x) [E], f0): phi sums to margin(x) - f0, f0 = mean background margin.  Numpy if

@@ -89,7 +89,7 @@ class Explanation:
     logit: np.ndarray       # [B] model log-odds / margin
     phi: np.ndarray         # [B, d] attributions
     base_value: float       # E[f] over the background, in phi's space
-    method: str             # "linear" | "kernel" | "tree"
+    method: str             # "linear" | "kernel" | "tree" | "tree_path"
     space: str              # "log-odds" | "probability"
 
 
@@ -323,6 +323,8 @@ class _EngineBase:
         m = self.resolve_method(method)
         if m == "tree":
             return self._explain_tree(X)
+        if m == "tree_path":
+            return self._explain_tree_path(X)
         if m == "linear":
             p, z, phi = self.predict_explain(X)
             return Explanation(p, z, phi, self.expected_value(), "linear", "log-odds")
@@ -592,7 +594,9 @@ class TreeInferenceEngine(_EngineBase):
     """GBDT family: standardize -> tree ensemble (fdx-gbdt/1 JSON, no pickle)."""
 
     kind = "gbdt"
-    methods = ("kernel", "tree")  # tree: interventional TreeSHAP of the margin (exact, log-odds)
+    # tree: interventional TreeSHAP of the margin (exact, log-odds, needs a background);
+    # tree_path: path-dependent TreeSHAP from the model's node covers (exact, log-odds, no background)
+    methods = ("kernel", "tree", "tree_path")
     default_method = "kernel"
 
     def __init__(self, ensemble, mean, var, scale, feature_names, device: str = "auto", source: str = "local",
@@ -716,6 +720,43 @@ class TreeInferenceEngine(_EngineBase):
         phi = h[: n * d].reshape(n, d).astype(np.float64)
         fx = h[n * d: n * d + n].astype(np.float64)
         return Explanation(1.0 / (1.0 + np.exp(-fx)), fx, phi, float(h[n * d + n]), "tree", "log-odds")
+
+    def resolve_method(self, method: str = "auto") -> str:
+        m = super().resolve_method(method)
+        if m == "tree_path" and getattr(self.ens, "cover", None) is None:
+            raise ValueError("tree_path SHAP needs node covers stored in the model (train with --gbdt-cover, or "
+                             "GBDTClassifier.compute_cover before save_model); it needs no background")
+        return m
+
+    def tree_path_explainer(self):
+        if getattr(self, "_pexpl", None) is None:
+            from ..models.explainers import TreePathExplainer
+
+            self._pexpl = TreePathExplainer(self.ens, self.mean, self.scale, device=str(self.device))
+        return self._pexpl
+
+    def _explain_tree_path(self, X: np.ndarray) -> "Explanation":
+        """Path-dependent TreeSHAP (log-odds): one staging upload, one launch sequence, one download."""
+        te = self.tree_path_explainer()
+        n, d = X.shape
+        if self.device.type != "cuda" or n == 0:
+            phi, fx, f0 = te.explain(X) if n else (np.zeros((0, d)), np.zeros(0), te.expected_value)
+            return Explanation(1.0 / (1.0 + np.exp(-fx)), fx, np.asarray(phi, np.float64), float(f0), "tree_path",
+                               "log-odds")
+        from ..ops.treeshap import treeshap_path
+
+        with self._lock, torch.cuda.stream(self._stream):
+            st = self._xstage
+            xd = st.upload(X)
+            o = st.dout
+            outs = (o[: n * d].view(n, d), o[n * d: n * d + n], o[n * d + n: n * d + 2 * n])
+            with _KernelTimer("treeshap_path_gbdt") as kt:
+                treeshap_path(xd, te, sync=False, out=outs)
+            h = st.download(n * d + 2 * n)
+            kt.observe()
+        phi = h[: n * d].reshape(n, d).astype(np.float64)
+        fx = h[n * d: n * d + n].astype(np.float64)
+        return Explanation(1.0 / (1.0 + np.exp(-fx)), fx, phi, float(te.expected_value), "tree_path", "log-odds")
 
     def _make_kernel_explainer(self):
         from ..models.explainers import TreeKernelExplainer

@@ -7,7 +7,8 @@ one [B, 30] matrix, scored, and explained -- by default with the model family's 
 xai_tasks.py:103-115 / api/worker.py:53; KernelSHAP for GBDT), and with KernelSHAP when
 ``FDX_XAI_METHOD=kernel`` (BASELINE config 4: the MFMA coalition GEMM, probability space,
 background = the training rows saved with the model; the stored ``explainer`` field says which)
-or interventional TreeSHAP when ``FDX_XAI_METHOD=tree`` -- then all rows are upserted in one DB
+or interventional TreeSHAP when ``FDX_XAI_METHOD=tree``, or path-dependent TreeSHAP from the
+model's stored node covers (no background file) when ``FDX_XAI_METHOD=tree_path`` -- then all rows are upserted in one DB
 transaction into BOTH
 ``transaction_results`` (status COMPLETED, prediction_score, shap_values) and
 ``shap_explanations`` (what /explain reads, with the explainer and its base value).  The model is

@@ -103,7 +103,7 @@ def run(settings: Settings | None = None, model_type: str = "logistic", cv_folds
         verbose: bool = True, cfg: TrainConfig | None = None, comm=None, gbdt_eval_metric=None,
         gbdt_early_stopping: int | None = None, gbdt_subsample: float = 1.0, gbdt_colsample_bytree: float = 1.0,
         gbdt_seed: int = 0, gbdt_monotone: str | None = None, gbdt_interaction: str | None = None,
-        gbdt_reg_alpha: float = 0.0, gbdt_max_delta_step: float = 0.0) -> dict:
+        gbdt_reg_alpha: float = 0.0, gbdt_max_delta_step: float = 0.0, gbdt_cover: str | None = None) -> dict:
     """Single process, or data parallel when ``comm`` spans several ranks (torchrun: one rank per
     GPU).  Every rank reads the table and derives the same split; each fits on its strided shard
     with RCCL all-reduced statistics, so all ranks hold the same model; rank 0 writes artifacts.
@@ -126,7 +126,14 @@ def run(settings: Settings | None = None, model_type: str = "logistic", cv_folds
 
     ``gbdt_reg_alpha`` / ``gbdt_max_delta_step``: xgboost's L1 regularisation of the leaf weights and
     its cap on |weight| (ops/gbdt.GBDTParams; both finite and >= 0, 0 = off), in every CV fold and in
-    the final fit.  Non-zero values land in the summary under "gbdt_reg"."""
+    the final fit.  Non-zero values land in the summary under "gbdt_reg".
+
+    ``gbdt_cover``: "hessian" or "count" -- after the final fit, node covers (ops/gbdt.node_cover) over
+    the REAL standardized training rows are stored in xgb_model.json, so the deployed engine serves
+    path-dependent TreeSHAP (``tree_path``) with no background file.  xgboost's sum_hess is taken
+    over the rows the trees were fit on, which here would include SMOTE's synthetic rows: the
+    covers deliberately describe the real data distribution instead.  Without it the saved model
+    is byte for byte what it always was."""
     s = settings or Settings.load()
     comm = comm if (comm is not None and comm.world_size > 1) else None
     lead = comm is None or comm.rank == 0
@@ -188,6 +195,13 @@ def run(settings: Settings | None = None, model_type: str = "logistic", cv_folds
         raise ValueError("--gbdt-interaction needs --model gbdt")
     elif gbdt_reg_alpha or gbdt_max_delta_step:
         raise ValueError("--gbdt-reg-alpha / --gbdt-max-delta-step need --model gbdt")
+    if gbdt_cover is not None:
+        if model_type != "gbdt":
+            raise ValueError("--gbdt-cover needs --model gbdt")
+        if gbdt_cover not in ("hessian", "count"):
+            raise ValueError("--gbdt-cover must be hessian or count")
+        if comm is not None and comm.world_size > 1:  # the int64 tables would add across ranks: not wired up
+            raise ValueError("--gbdt-cover runs in a single process (data-parallel covers are not implemented)")
     cv_scores = []
     from dataclasses import asdict
 
@@ -286,6 +300,12 @@ def run(settings: Settings | None = None, model_type: str = "logistic", cv_folds
     if not lead:
         comm.barrier()
         return {"test_auc": float(auc), "cv_scores": cv_scores, "rank": comm.rank}
+    if gbdt_cover is not None:
+        from .ops import gbdt as gb_ops
+
+        res.ensemble = res.ensemble.with_cover(
+            gb_ops.node_cover(res.standardize(Xtr), res.ensemble, gbdt_cover).cpu().numpy(), gbdt_cover)
+        res._dens = None
     paths = _save(model_type, res, names, model_dir, cfg)
     # KernelSHAP background (shap.sample of the training rows) for the async XAI worker
     from .serve.engine import sample_background, save_background
@@ -306,6 +326,8 @@ def run(settings: Settings | None = None, model_type: str = "logistic", cv_folds
         summary["gbdt_monotone"] = {names[f]: c for f, c in sorted(gbdt_params.monotone_constraints.items()) if c}
     if gbdt_params is not None and gbdt_params.interaction_constraints:
         summary["gbdt_interaction"] = [[names[f] for f in g] for g in gbdt_params.interaction_constraints]
+    if gbdt_cover is not None:
+        summary["gbdt_cover"] = {"kind": gbdt_cover, "rows": int(Xtr.shape[0])}
     if gbdt_params is not None and gbdt_params.reg is not None:
         summary["gbdt_reg"] = {"reg_alpha": gbdt_params.reg[0], "max_delta_step": gbdt_params.reg[1]}
     try:
@@ -533,6 +555,10 @@ def main(argv=None):
     ap.add_argument("--gbdt-max-delta-step", type=float, default=0.0,
                     help="cap on a leaf weight's magnitude before the learning rate (xgboost's max_delta_step, its "
                          "advice for extremely imbalanced classes; 0: no cap)")
+    ap.add_argument("--gbdt-cover", default=None, choices=["hessian", "count"],
+                    help="store node covers over the real standardized training rows (not the SMOTE samples) in "
+                         "xgb_model.json: hessian = xgboost's sum_hess, count = rows per node; the served model then "
+                         "explains with path-dependent TreeSHAP (FDX_XAI_METHOD=tree_path) without a background file")
     a = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO)
     comm = None
@@ -552,7 +578,8 @@ def main(argv=None):
                   gbdt_early_stopping=a.gbdt_early_stopping, gbdt_subsample=a.gbdt_subsample,
                   gbdt_colsample_bytree=a.gbdt_colsample_bytree, gbdt_seed=a.gbdt_seed,
                   gbdt_monotone=a.gbdt_monotone, gbdt_interaction=a.gbdt_interaction,
-                  gbdt_reg_alpha=a.gbdt_reg_alpha, gbdt_max_delta_step=a.gbdt_max_delta_step)
+                  gbdt_reg_alpha=a.gbdt_reg_alpha, gbdt_max_delta_step=a.gbdt_max_delta_step,
+                  gbdt_cover=a.gbdt_cover)
     finally:
         if comm is not None:
             comm.close()
