@@ -914,6 +914,15 @@ PYBIND11_MODULE(_fdx_native, m) {
                               P<float>(phi), P<float>(fx), P<float>(f0o), S(s));
   });
   m.def("treeshap_path_trees_in_lds", &fdx::treeshap_path_trees_in_lds);
+  m.def("treeshap_interactions", [](u Xs, int ldx, int E, int d, u feat, u thr, u leaf, u frac, u dleft, int T,
+                                    int depth, float base, float f0, int leaf_exp, bool stream_trees, u inter, u phi,
+                                    u fx, u f0o, u s) {
+    fdx::launch_treeshap_interactions(P<const float>(Xs), ldx, E, d, P<const int>(feat), P<const float>(thr),
+                                      P<const float>(leaf), P<const float>(frac), P<const uint8_t>(dleft), T, depth,
+                                      base, f0, leaf_exp, stream_trees, P<double>(inter), P<float>(phi), P<float>(fx),
+                                      P<float>(f0o), S(s));
+  });
+  m.def("treeshap_interactions_trees_in_lds", &fdx::treeshap_interactions_trees_in_lds);
   m.def("tree_cover", [](u X, int64_t n, int ld, int d, u feat, u thr, u leaf, u dleft, int T, int depth, float base,
                          int kind, u ws, u cover, u s) {
     fdx::launch_tree_cover(P<const float>(X), n, ld, d, P<const int>(feat), P<const float>(thr), P<const float>(leaf),

@@ -444,6 +444,17 @@ void launch_treeshap_path(const float* Xs, int ldx, int n_expl, int d, const int
                           hipStream_t stream);
 // whether launch_treeshap_path keeps leaves, split features and fractions in LDS for this shape
 bool treeshap_path_trees_in_lds(int d, int ntrees, int depth);
+// SHAP interaction values of the same game (treeshap_interact.hip): inter fp64 [n_expl][d][d]
+// (symmetric, row i sums to phi_i), phi fp32 [n_expl][d], fx and f0 as launch_treeshap_path.
+// leaf_exp: the smallest e with max |leaf| <= 2^e (the fixed-point scale is 2^(e - 46)).
+// stream_trees keeps the per-tree constants out of LDS even where they fit; the result is the same
+// bit for bit.
+void launch_treeshap_interactions(const float* Xs, int ldx, int n_expl, int d, const int* feat, const float* thr,
+                                  const float* leaf, const float* frac, const uint8_t* dleft, int ntrees,
+                                  int depth, float base_margin, float f0, int leaf_exp, bool stream_trees,
+                                  double* inter, float* phi, float* fx_out, float* f0_out, hipStream_t stream);
+// whether launch_treeshap_interactions keeps leaves, split features and fractions in LDS
+bool treeshap_interactions_trees_in_lds(int d, int ntrees, int depth);
 // node covers (treecover.hip): cover int64 [ntrees][2^(depth+1)] by heap node over the rows X;
 // kind 0 = row counts, 1 = sums of llrint(p (1 - p) 2^30).  margin_ws: fp32 [n] scratch, needed by
 // kind 1 when ntrees exceeds tree_cover_chunk_trees(depth) (null otherwise)

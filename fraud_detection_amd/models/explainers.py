@@ -31,7 +31,8 @@ XGBoost model):
     (treeshap.hip), orders of magnitude less work than KernelSHAP on trees;
   * ``TreePathExplainer`` -- path-dependent TreeSHAP of the GBDT margin from the node covers stored
     in the model (treeshap_path.hip): exact, no background, NaN follows the learned default
-    direction -- xgboost's pred_contribs;
+    direction -- xgboost's pred_contribs; and the SHAP interaction values of the same game
+    (treeshap_interact.hip) -- pred_interactions, shap_interaction_values;
   * ``FunctionKernelExplainer`` -- any callable on device tensors (e.g. a torch model): masked rows
     are built in chunks on the device, the model is called on them, and the shared WLS operator
     projects the coalition values.
@@ -605,6 +606,74 @@ def treeshap_path_reference(Xs: np.ndarray, ens) -> tuple:
     return phi, fx, path_expected_value(ens, frac)
 
 
+def treeshap_interactions_reference(Xs: np.ndarray, ens) -> tuple:
+    """fp64 per-leaf oracle of the SHAP interaction values of treeshap_path_reference's game on
+    STANDARDIZED rows (treeshap_interact.hip's form): for leaf L with value v, distinct path
+    features M (m = |M|) and the merged z_j, o_j, every pair i != j in M gets
+        Phi_ij += v (o_i - z_i) (o_j - z_j) sum_s s! (m - s - 2)! / (2 (m - 1)!) c_s,
+    c_s the coefficient of y^s in prod_{k in M, k != i, j} (z_k + o_k y); the diagonal is
+    Phi_ii = phi_i - sum_{j != i} Phi_ij with phi the leaf's ordinary Shapley values.  The matrix
+    is symmetric, row i sums to phi_i and everything to margin(x) - f0 (shap's and xgboost's
+    convention).  Returns (inter [E, d, d], phi [E, d], margin(x) [E], f0)."""
+    Xs = np.asarray(Xs, np.float32)
+    frac = path_fractions(ens)
+    xw = path_direction_bits(Xs, ens)
+    D = ens.depth
+    E, d = Xs.shape
+    inter = np.zeros((E, d, d))
+    phi = np.zeros((E, d))
+    fact = [math.factorial(i) for i in range(D + 1)]
+    feat = ens.feat.tolist()
+
+    def poly(M, skip, z, o):
+        c = [1.0]
+        for f in M:
+            if f in skip:
+                continue
+            c = [(c[s] * z[f] if s < len(c) else 0.0) + (c[s - 1] * o[f] if s else 0.0) for s in range(len(c) + 1)]
+        return c
+
+    for t in range(ens.n_trees):
+        for l in range(1 << D):
+            heap = (1 << D) + l
+            path, dead = [], False
+            for j in range(D):
+                k, c = heap >> (D - j), heap >> (D - j - 1)
+                if feat[t][k - 1] < 0:
+                    dead = dead or bool(c & 1)
+                else:
+                    path.append((k, c))
+            if dead or not path:
+                continue
+            v = float(ens.leaf[t, l])
+            M = sorted({feat[t][k - 1] for k, _ in path})
+            m = len(M)
+            for e in range(E):
+                xb = int(xw[t, e])
+                z = {f: 1.0 for f in M}
+                o = {f: 1.0 for f in M}
+                for k, c in path:
+                    f = feat[t][k - 1]
+                    z[f] *= frac[t, c]
+                    if ((xb >> k) & 1) != (c & 1):
+                        o[f] = 0.0
+                for i in M:
+                    W = sum(fact[s] * fact[m - s - 1] / fact[m] * cs for s, cs in enumerate(poly(M, (i,), z, o)))
+                    phi[e, i] += v * (o[i] - z[i]) * W
+                for a in range(m):
+                    for b in range(a + 1, m):
+                        i, j = M[a], M[b]
+                        W = sum(fact[s] * fact[m - s - 2] / (2 * fact[m - 1]) * cs
+                                for s, cs in enumerate(poly(M, (i, j), z, o)))
+                        inter[e, i, j] += v * (o[i] - z[i]) * (o[j] - z[j]) * W
+    iu = np.triu_indices(d, 1)
+    inter[:, iu[1], iu[0]] = inter[:, iu[0], iu[1]]          # one value per pair: symmetric bit for bit
+    idx = np.arange(d)
+    inter[:, idx, idx] = phi - inter.sum(2)
+    fx = _margins_from_bits(xw, ens).astype(np.float64)
+    return inter, phi, fx, path_expected_value(ens, frac)
+
+
 class TreePathExplainer:
     """Path-dependent TreeSHAP of a tree ensemble (ops/gbdt.TreeEnsemble on standardized rows) over
     RAW inputs, in margin (log-odds) space -- xgboost's predict(pred_contribs=True) and
@@ -655,6 +724,24 @@ class TreePathExplainer:
         if X.shape[0] == 0:
             return np.zeros((0, self.d)), np.zeros(0), self.f0
         return treeshap_path_reference(_standardize(X, self.mean, self.scale), self.ens)
+
+    def shap_interaction_values(self, X) -> np.ndarray:
+        """[E, d, d] -- shap.TreeExplainer(model).shap_interaction_values, xgboost's pred_interactions
+        without its bias row and column."""
+        return self.explain_interactions(X)[0]
+
+    def explain_interactions(self, X):
+        """-> (inter [E, d, d], phi [E, d], margin(x) [E], f0) in log-odds space: inter[e] is
+        symmetric, its row i sums to phi[e, i] and the whole matrix to margin(x) - f0
+        (csrc/kernels/treeshap_interact.hip on a GPU explainer, the fp64 per-leaf form on CPU)."""
+        X = np.ascontiguousarray(X, np.float32)
+        if self.device.type == "cuda":
+            from ..ops.treeshap import treeshap_interactions
+
+            return treeshap_interactions(torch.from_numpy(X).to(self.device), self)
+        if X.shape[0] == 0:
+            return np.zeros((0, self.d, self.d)), np.zeros((0, self.d)), np.zeros(0), self.f0
+        return treeshap_interactions_reference(_standardize(X, self.mean, self.scale), self.ens)
 
 
 class FunctionKernelExplainer:

@@ -4,7 +4,10 @@
   (n_estimators, learning_rate, max_depth, reg_lambda, min_child_weight, gamma, max_bin,
   scale_pos_weight, base_score, monotone_constraints, interaction_constraints, reg_alpha,
   max_delta_step) over numpy arrays or torch tensors; device kernels on a GPU
-  tensor, the numpy oracle on CPU.  Models serialise to JSON (no pickle).
+  tensor, the numpy oracle on CPU.  Models serialise to JSON (no pickle).  With node covers
+  in the model (``fit(..., record_cover=True)`` or ``compute_cover``) it explains itself without a
+  background: ``predict_contribs`` (xgboost's pred_contribs, [n, d + 1]) and
+  ``predict_interactions`` (pred_interactions, [n, d + 1, d + 1]).
 * ``GBDTPipeline`` -- the reference's per-fold recipe on device: StandardScaler fit on the
   fold's rows -> SMOTE (MFMA k-NN + Philox interpolation, fp32 rows) -> boosting -> exact AUC.
   ``scale_pos_weight="auto"`` (default) is neg/pos of the rows the trees are fit on, i.e. AFTER
@@ -245,9 +248,30 @@ class GBDTClassifier:
         ``predict_margin``.  A NaN follows the learned default direction.  ``iteration_range=(0, k)``
         uses the first k trees and their covers.  Needs ``compute_cover`` (or
         ``fit(..., record_cover=True)``) first."""
+        expl, Xh = self._path_explainer(X, iteration_range, "predict_contribs")
+        phi, _, f0 = expl.explain(Xh)
+        return np.concatenate([phi, np.full((phi.shape[0], 1), f0)], 1)
+
+    def predict_interactions(self, X, iteration_range=None) -> np.ndarray:
+        """xgboost's ``predict(pred_interactions=True)``: float64 [n, d + 1, d + 1] SHAP interaction
+        values of the margin from the stored node covers.  ``[:, :d, :d]`` holds the interactions
+        (symmetric), ``[:, d, d]`` the bias f0 and the rest of the last row and column is 0, so every
+        ``[:, i, :]`` sums to column i of ``predict_contribs`` and the whole matrix to
+        ``predict_margin``.  Covers, NaN routing and ``iteration_range`` as ``predict_contribs``,
+        whose cached explainer it shares."""
+        expl, Xh = self._path_explainer(X, iteration_range, "predict_interactions")
+        inter, _, _, f0 = expl.explain_interactions(Xh)
+        n, d = inter.shape[0], inter.shape[1]
+        out = np.zeros((n, d + 1, d + 1))
+        out[:, :d, :d] = inter
+        out[:, d, d] = f0
+        return out
+
+    def _path_explainer(self, X, iteration_range, who: str):
+        """(the cached TreePathExplainer of the first k trees on X's device, X as fp32 numpy)."""
         self._check()
         if self.ensemble.cover is None:
-            raise ValueError("predict_contribs needs node covers: call compute_cover(X) (ops/gbdt.node_cover) or "
+            raise ValueError(f"{who} needs node covers: call compute_cover(X) (ops/gbdt.node_cover) or "
                              "fit(..., record_cover=True) first")
         from .explainers import TreePathExplainer
 
@@ -261,8 +285,7 @@ class GBDTClassifier:
             cache = (key, TreePathExplainer(self.ensemble.head(k), np.zeros(d), np.ones(d), device=str(dev)))
             self._pexpl = cache
         Xh = X.detach().cpu().numpy() if isinstance(X, torch.Tensor) else np.asarray(X)
-        phi, _, f0 = cache[1].explain(np.ascontiguousarray(Xh, np.float32))
-        return np.concatenate([phi, np.full((phi.shape[0], 1), f0)], 1)
+        return cache[1], np.ascontiguousarray(Xh, np.float32)
 
     def feature_importance(self, kind: str = "gain") -> np.ndarray:
         """``TreeEnsemble.feature_importance``: "gain", "weight", "total_gain", "cover", "total_cover"."""

@@ -1,6 +1,10 @@
 """K7b interventional TreeSHAP device wrapper (csrc/kernels/treeshap.hip): exact SHAP values of a
-tree ensemble's margin (log-odds) against a background set, one workgroup per explanation."""
+tree ensemble's margin (log-odds) against a background set, one workgroup per explanation; and the
+wrappers of the two background-free kernels on the model's node covers, path-dependent TreeSHAP
+(csrc/kernels/treeshap_path.hip) and its SHAP interaction values (csrc/kernels/treeshap_interact.hip)."""
 from __future__ import annotations
+
+import math
 
 import numpy as np
 import torch
@@ -78,6 +82,66 @@ def treeshap_path(X: torch.Tensor, expl, sync: bool = True, out=None):
     if not sync:
         return phi, fx, f0
     return phi.cpu().numpy().astype(np.float64), fx.cpu().numpy().astype(np.float64), float(expl.f0)
+
+
+def treeshap_interactions_lds_resident(d: int, n_trees: int, depth: int) -> bool:
+    """Whether launch_treeshap_interactions keeps leaves, split features and fractions in LDS."""
+    return bool(native().treeshap_interactions_trees_in_lds(int(d), int(n_trees), int(depth)))
+
+
+def leaf_exponent(leaf) -> int:
+    """The smallest integer e with max |leaf| <= 2^e (0 for an all-zero model): the fixed-point
+    sums of treeshap_interact.hip are in units of 2^(e - 46).  ValueError on a non-finite leaf."""
+    v = np.abs(np.asarray(leaf, np.float64))
+    if not np.all(np.isfinite(v)):
+        raise ValueError("SHAP interaction values need finite leaf values")
+    vmax = float(v.max()) if v.size else 0.0
+    if vmax == 0.0:
+        return 0
+    mant, ex = math.frexp(vmax)          # vmax = mant * 2^ex, 0.5 <= mant < 1
+    return ex - 1 if mant == 0.5 else ex
+
+
+def treeshap_interactions(X: torch.Tensor, expl, sync: bool = True, out=None, *, stream_trees: bool = False):
+    """SHAP interaction values of the path-dependent game (csrc/kernels/treeshap_interact.hip).
+    X [E, d] RAW fp32 on device (standardized on device with the model's scaler; a NaN stays NaN
+    and follows default_left) -> (inter [E, d, d], phi [E, d], margin(x) [E], f0): inter[e] is
+    symmetric bit for bit, its row i sums to phi[e, i] and the whole matrix to margin(x) - f0.
+    Float64 numpy if ``sync`` else device tensors (inter float64, the rest float32; ``out``:
+    preallocated (inter, phi, fx, f0) device tensors).  E = 0 launches nothing and returns empty
+    results of these shapes.  ``stream_trees`` reads the per-tree constants from L2 even where they
+    fit in LDS: the same result bit for bit (the sums are integers), there for tests and timing."""
+    _check_x(X, expl.d)
+    m = native()
+    dev = X.device
+    t = _device_path_design(expl, dev)
+    from .scaler import scale_cast
+
+    E, d = X.shape[0], expl.d
+    ens = expl.ens
+    e2 = leaf_exponent(ens.leaf)
+    if out is not None:
+        inter, phi, fx, f0 = out
+        if (inter.shape != (E, d, d) or inter.dtype != torch.float64 or not inter.is_contiguous()
+                or phi.shape != (E, d) or not phi.is_contiguous() or fx.shape[0] != E or f0.shape[0] < E):
+            raise ValueError("out = (inter [E, d, d] float64 contiguous, phi [E, d] contiguous, fx [E], f0 [E]) "
+                             "device tensors")
+    else:
+        inter = torch.empty((E, d, d), device=dev, dtype=torch.float64)
+        phi, fx, f0 = _outputs(E, d, dev, None)
+    if E == 0:
+        if not sync:
+            return inter, phi, fx, f0
+        return np.zeros((0, d, d)), np.zeros((0, d)), np.zeros(0), float(expl.f0)
+    Xs = scale_cast(X, t["stats"], out_dtype="f32")  # [E, 32]
+    m.treeshap_interactions(ptr(Xs), Xs.stride(0), E, d, ptr(t["feat"]), ptr(t["thr"]), ptr(t["leaf"]),
+                            ptr(t["frac"]), ptr(t["dleft"]), ens.n_trees, ens.depth, float(ens.base_margin),
+                            float(expl.f0), e2, bool(stream_trees), ptr(inter), ptr(phi), ptr(fx), ptr(f0),
+                            stream_of(X))
+    if not sync:
+        return inter, phi, fx, f0
+    return (inter.cpu().numpy(), phi.cpu().numpy().astype(np.float64), fx.cpu().numpy().astype(np.float64),
+            float(expl.f0))
 
 
 def treeshap(X: torch.Tensor, expl, sync: bool = True, out=None):
