@@ -33,18 +33,20 @@
 // xw[t] for x and, per (coalition, tree), Zt = the z-bit of each node's feature.  The effective
 // direction bits are then ONE bitfield insert, R = (Zt & xw) | (~Zt & bw), and the walk is 2 VALU
 // ops per level on a 1-based heap.  xw / bw are wave-uniform (a wave holds 64 coalitions x one
-// background row), leaves sit in LDS.
+// background row), leaves sit in LDS.  The heap layout, the direction bits and the walk are the tree
+// explainer family's: tree_explain.h.
 //
 // MFMA operand maps (cdna_hip_programming.md §3): lane l (r = l & 31, h = l >> 5) supplies
 // A[row r][k = 8h + j] and B[k = 8h + j][col r], j = 0..7 -> both are 16 contiguous bytes of a
 // row (U row b for A, Z row s for B); accumulator row = (i & 3) + 8 (i >> 2) + 4 h, col = r.
-#include "common.h"
 #include "launchers.h"
+#include "tree_explain.h"
 
 namespace fdx {
 namespace {
 
 constexpr int kThreads = 256;
+static_assert(kThreads == kTreeThreads, "the tree kernel stages x's direction bits with the family's stride");
 constexpr int kWaves = 4;
 constexpr int kMaxBg = 128;      // 4 background tiles of 32
 constexpr int kMaxS = 4096;      // coalitions per design
@@ -52,7 +54,6 @@ constexpr int kMaxParts = 8;
 constexpr float kNullAcc = 70.0f;     // exact in bf16; sigma = 1 / (1 + 2^70)
 constexpr float kPairShift = 40.0f;   // exp2 argument shift of the paired-reciprocal epilogue
 constexpr int kTreeLdsLeaves = 8192;  // leaves (floats) staged in LDS by the tree kernel
-constexpr int kMaxTrees = 2048;
 
 __device__ __forceinline__ short bf16_bits(float f) { return (short)f32_to_bf16(f); }
 
@@ -611,15 +612,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
 // ------------------------------------------------------------------------------------------------
 // Tree ensemble (depth D <= 5: the 31 internal nodes of a tree fit one 32-bit mask)
 // ------------------------------------------------------------------------------------------------
-// Walk one tree from the effective direction bits R1 (bit n + 1 = node n goes right; heap 1-based)
-template <int D>
-__device__ __forceinline__ int walk(uint32_t R1) {
-  int node = 1;
-#pragma unroll
-  for (int l = 0; l < D; ++l) node = (node << 1) | (int)((R1 >> node) & 1u);
-  return node - (1 << D);  // leaf index
-}
-
+// The walks run from the effective direction bits R1 (tree_explain.h: bit n + 1 = node n goes right)
 template <int D, bool LOGITS, bool LEAF_LDS>
 __global__ __launch_bounds__(kThreads) void kernelshap_tree_kernel(
     const float* __restrict__ Xs, int ldx, int d, const int* __restrict__ feat, const float* __restrict__ thr,
@@ -632,7 +625,7 @@ __global__ __launch_bounds__(kThreads) void kernelshap_tree_kernel(
   float* ys = dyn;                          // this part's coalitions
   float* lf = dyn + ((S_pad + 3) & ~3);     // leaves [T][NL] (LEAF_LDS)
   __shared__ float xs[32];
-  __shared__ uint32_t xw[kMaxTrees];        // x's direction bits per tree, pre-shifted (bit n + 1)
+  __shared__ uint32_t xw[kTreeMaxTrees];   // x's direction bits per tree, pre-shifted (bit n + 1)
   __shared__ float red[8];
   __shared__ float ph[32];
   __shared__ int flag;
@@ -646,14 +639,7 @@ __global__ __launch_bounds__(kThreads) void kernelshap_tree_kernel(
     for (int i = threadIdx.x; i < T * NL; i += kThreads) lf[i] = leaf[i];
   }
   __syncthreads();
-  for (int t = threadIdx.x; t < T; t += kThreads) {
-    uint32_t m = 0;
-    for (int n = 0; n < NI; ++n) {
-      const int f = feat[t * NI + n];
-      if (f >= 0 && !(xs[f] < thr[t * NI + n])) m |= 2u << n;
-    }
-    xw[t] = m;
-  }
+  stage_direction_bits<NI>(xs, feat, thr, nullptr, T, xw);
   __syncthreads();
   const float* LF = LEAF_LDS ? lf : leaf;
   const float inv_nb = 1.0f / (float)n_bg;
@@ -681,7 +667,7 @@ __global__ __launch_bounds__(kThreads) void kernelshap_tree_kernel(
         for (int j = 0; j < 32; ++j) {
           if (j < nb) {
             const uint32_t R1 = (Zt & xt) | (~Zt & bt[j]);
-            mg[j] += lt[walk<D>(R1)];
+            mg[j] += lt[tree_leaf<D>(R1)];
           }
         }
       }
@@ -695,14 +681,14 @@ __global__ __launch_bounds__(kThreads) void kernelshap_tree_kernel(
   float z0s = 0.0f;
   for (int b = threadIdx.x; b < n_bg; b += kThreads) {
     float m = base_margin;
-    for (int t = 0; t < T; ++t) m += LF[t * NL + walk<D>(bw[(int64_t)t * bw_ld + b])];
+    for (int t = 0; t < T; ++t) m += LF[t * NL + tree_leaf<D>(bw[(int64_t)t * bw_ld + b])];
     z0s += LOGITS ? m : fast_sigmoid(m);
   }
   z0s = wave_sum(z0s);
   if (lane == 0) red[wv] = z0s;
   if (threadIdx.x == 0) {
     float m = base_margin;
-    for (int t = 0; t < T; ++t) m += LF[t * NL + walk<D>(xw[t])];
+    for (int t = 0; t < T; ++t) m += LF[t * NL + tree_leaf<D>(xw[t])];
     red[4] = m;
   }
   __syncthreads();
@@ -828,36 +814,20 @@ void launch_kernelshap_tree(const float* Xs, int ldx, int n_expl, int d, const i
                             const float* Amat, const float* Az, int link, float* phi, float* fx_out,
                             float* f0_out, float* ws, unsigned* cnt, hipStream_t stream) {
   check_design(d, S, S_pad, parts);
-  if (depth < 1 || depth > 5) throw std::runtime_error("kernelshap_tree: depth must be in [1, 5]");
-  if (ntrees < 1 || ntrees > kMaxTrees) throw std::runtime_error("kernelshap_tree: 1 <= trees <= 2048");
+  if (depth < 1 || depth > kTreeMaxDepth) throw std::runtime_error("kernelshap_tree: depth must be in [1, 5]");
+  if (ntrees < 1 || ntrees > kTreeMaxTrees) throw std::runtime_error("kernelshap_tree: 1 <= trees <= 2048");
   if (n_bg < 1 || bw_ld < n_bg) throw std::runtime_error("kernelshap_tree: bad background");
   if (parts > 1 && (ws == nullptr || cnt == nullptr)) throw std::runtime_error("kernelshap: parts > 1 needs ws/cnt");
   if (n_expl <= 0) return;
   const dim3 grid((unsigned)((int64_t)n_expl * parts));
   const bool lds_leaves = ntrees * (1 << depth) <= kTreeLdsLeaves;
   const size_t lds = ((size_t)((S_pad + 3) & ~3) + (lds_leaves ? (size_t)ntrees << depth : 0)) * sizeof(float);
-  const bool logits = link == 2;
-#define FDX_KT(D_, LG, LL)                                                                                 \
-  kernelshap_tree_kernel<D_, LG, LL><<<grid, kThreads, lds, stream>>>(                                     \
-      Xs, ldx, d, feat, thr, leaf, ntrees, base_margin, bw, bw_ld, n_bg, Zm, S, S_pad, parts, Amat, Az, link, \
-      phi, fx_out, f0_out, ws, cnt)
-#define FDX_KT_D(D_)                                              \
-  do {                                                            \
-    if (logits) {                                                 \
-      if (lds_leaves) FDX_KT(D_, true, true); else FDX_KT(D_, true, false);   \
-    } else {                                                      \
-      if (lds_leaves) FDX_KT(D_, false, true); else FDX_KT(D_, false, false); \
-    }                                                             \
-  } while (0)
-  switch (depth) {
-    case 1: FDX_KT_D(1); break;
-    case 2: FDX_KT_D(2); break;
-    case 3: FDX_KT_D(3); break;
-    case 4: FDX_KT_D(4); break;
-    default: FDX_KT_D(5); break;
-  }
-#undef FDX_KT_D
-#undef FDX_KT
+  dispatch_depth(depth, lds_leaves, [&](auto D, auto LL) {
+    const auto kernel = link == 2 ? kernelshap_tree_kernel<decltype(D)::value, true, decltype(LL)::value>
+                                  : kernelshap_tree_kernel<decltype(D)::value, false, decltype(LL)::value>;
+    kernel<<<grid, kThreads, lds, stream>>>(Xs, ldx, d, feat, thr, leaf, ntrees, base_margin, bw, bw_ld, n_bg, Zm, S,
+                                            S_pad, parts, Amat, Az, link, phi, fx_out, f0_out, ws, cnt);
+  });
   check_launch("kernelshap_tree");
 }
 

@@ -30,27 +30,18 @@
 // no-return LDS atomics both measured flat).  A divergence-free variant with lanes over leaves
 // (reachability of all 2^D leaves tested with bit masks per background row) measured slower,
 // 1.36-1.42 ms: it tests every leaf where the walk visits only reachable ones.
-#include "common.h"
+//
+// The heap layout, the direction bits, the walk and the fixed-order sums are the family's:
+// tree_explain.h.
 #include "launchers.h"
+#include "tree_explain.h"
 
 namespace fdx {
 namespace {
 
-constexpr int kTSThreads = 256;
-constexpr int kTSMaxTrees = 2048;
-constexpr int kTSMaxDepth = 5;
-
-// Shapley weights of a leaf term with a = |A|, b = |B| (a + b <= depth): positive (features in
-// A) (a-1)! b! / (a+b)!, negative (features in B) a! (b-1)! / (a+b)!.
-__device__ __forceinline__ float fact(int n) {
-  float r = 1.0f;
-  for (int i = 2; i <= n; ++i) r *= (float)i;
-  return r;
-}
-
 struct LeafCtx {
   const float* lf;    // this tree's leaves
-  float* ph;          // LDS phi table [feature][kTSThreads] (this thread's column at + tid)
+  float* ph;          // LDS phi table [feature][kTreeThreads] (this thread's column at + tid)
   const float* wp;    // [6][6] weights
   const float* wn;
 };
@@ -63,8 +54,8 @@ __device__ __forceinline__ void walk_pairs(int k, uint32_t A, uint32_t B, uint32
     const float v = c.lf[k - (1 << D)];
     const int a = __popc(A), b = __popc(B);
     const float pw = v * c.wp[a * 6 + b], nw = v * c.wn[a * 6 + b];
-    for (uint32_t m = A; m; m &= m - 1u) c.ph[(__ffs(m) - 1) * kTSThreads] += pw;
-    for (uint32_t m = B; m; m &= m - 1u) c.ph[(__ffs(m) - 1) * kTSThreads] -= nw;
+    for (uint32_t m = A; m; m &= m - 1u) c.ph[(__ffs(m) - 1) * kTreeThreads] += pw;
+    for (uint32_t m = B; m; m &= m - 1u) c.ph[(__ffs(m) - 1) * kTreeThreads] -= nw;
   } else {
     const int f = ft[k - 1];
     int c1 = 2 * k, c2 = 0;
@@ -88,57 +79,36 @@ __device__ __forceinline__ void walk_pairs(int k, uint32_t A, uint32_t B, uint32
   }
 }
 
-template <int D>
-__device__ __forceinline__ float tree_margin(uint32_t bits, const float* __restrict__ lf) {
-  int node = 1;
-#pragma unroll
-  for (int l = 0; l < D; ++l) node = (node << 1) | (int)((bits >> node) & 1u);
-  return lf[node - (1 << D)];
-}
-
 template <int D, bool LEAF_LDS>
-__global__ __launch_bounds__(kTSThreads) void treeshap_kernel(
+__global__ __launch_bounds__(kTreeThreads) void treeshap_kernel(
     const float* __restrict__ Xs, int ldx, int d, const int* __restrict__ feat, const float* __restrict__ thr,
     const float* __restrict__ leaf, int T, float base_margin, const uint32_t* __restrict__ bw, int bw_ld,
     int n_bg, float f0, float* __restrict__ phi, float* __restrict__ fx_out, float* __restrict__ f0_out) {
   constexpr int NI = (1 << D) - 1, NL = 1 << D;
-  // dynamic LDS: phi table [d][kTSThreads] | x's direction bits [T] | (LEAF_LDS) leaves [T][NL]
+  // dynamic LDS: phi table [d][kTreeThreads] | x's direction bits [T] | (LEAF_LDS) leaves [T][NL]
   // and split features [T][NI] -- the walk reads one feature per level on a dependent chain,
   // an L2 round trip each from global memory
   extern __shared__ __attribute__((aligned(16))) float dyn[];
   float* ph = dyn;
-  uint32_t* xw = reinterpret_cast<uint32_t*>(dyn + d * kTSThreads);
-  float* lfs = reinterpret_cast<float*>(xw + T);
-  int* fts = reinterpret_cast<int*>(lfs + (LEAF_LDS ? T * NL : 0));
+  uint32_t* xw = reinterpret_cast<uint32_t*>(dyn + d * kTreeThreads);
   __shared__ float xs[32];
   __shared__ float wtab[2][36];
-  __shared__ float red[kTSThreads / kWave];
+  __shared__ float red[kTreeThreads / kWave];
   const int e = blockIdx.x, tid = threadIdx.x;
   if (tid < 32) xs[tid] = tid < d ? Xs[(int64_t)e * ldx + tid] : 0.0f;
+  // Shapley weights of a leaf term with a = |A|, b = |B| (a + b <= depth): positive (features in
+  // A) (a-1)! b! / (a+b)!, negative (features in B) a! (b-1)! / (a+b)!
   if (tid < 36) {
     const int a = tid / 6, b = tid % 6;
-    const float den = fact(a + b);
-    wtab[0][tid] = (a >= 1) ? fact(a - 1) * fact(b) / den : 0.0f;
-    wtab[1][tid] = (b >= 1) ? fact(a) * fact(b - 1) / den : 0.0f;
+    const float den = shap_fact(a + b);
+    wtab[0][tid] = (a >= 1) ? shap_fact(a - 1) * shap_fact(b) / den : 0.0f;
+    wtab[1][tid] = (b >= 1) ? shap_fact(a) * shap_fact(b - 1) / den : 0.0f;
   }
-  for (int i = tid; i < d * kTSThreads; i += kTSThreads) ph[i] = 0.0f;
-  if constexpr (LEAF_LDS) {
-    for (int i = tid; i < T * NL; i += kTSThreads) lfs[i] = leaf[i];
-    for (int i = tid; i < T * NI; i += kTSThreads) fts[i] = feat[i];
-  }
+  for (int i = tid; i < d * kTreeThreads; i += kTreeThreads) ph[i] = 0.0f;
+  const TreeConsts tc = stage_tree_consts<D, LEAF_LDS, false>(reinterpret_cast<float*>(xw + T), leaf, feat, nullptr, T);
   __syncthreads();
-  // x's direction bits per tree (bit n + 1: internal node n sends x right; pass-through: left)
-  for (int t = tid; t < T; t += kTSThreads) {
-    uint32_t m = 0;
-    for (int n = 0; n < NI; ++n) {
-      const int f = feat[t * NI + n];
-      if (f >= 0 && !(xs[f] < thr[t * NI + n])) m |= 2u << n;
-    }
-    xw[t] = m;
-  }
+  stage_direction_bits<NI>(xs, feat, thr, nullptr, T, xw);
   __syncthreads();
-  const float* LF = LEAF_LDS ? lfs : leaf;
-  const int* FT = LEAF_LDS ? fts : feat;
   LeafCtx c{nullptr, ph + tid, wtab[0], wtab[1]};
   const int npairs = T * n_bg;
   // (tree, background) pairs in tree-major order; the next pair's background bits are loaded
@@ -146,36 +116,18 @@ __global__ __launch_bounds__(kTSThreads) void treeshap_kernel(
   int p = tid;
   uint32_t zb_next = 0;
   if (p < npairs) zb_next = bw[(int64_t)(p / n_bg) * bw_ld + (p % n_bg)];
-  for (; p < npairs; p += kTSThreads) {
+  for (; p < npairs; p += kTreeThreads) {
     const int t = p / n_bg;
     const uint32_t zb = zb_next;
-    const int pn = p + kTSThreads;
+    const int pn = p + kTreeThreads;
     if (pn < npairs) zb_next = bw[(int64_t)(pn / n_bg) * bw_ld + (pn % n_bg)];
-    c.lf = LF + t * NL;
-    walk_pairs<D, 0>(1, 0u, 0u, xw[t], zb, FT + t * NI, c);
+    c.lf = tc.leaf + t * NL;
+    walk_pairs<D, 0>(1, 0u, 0u, xw[t], zb, tc.feat + t * NI, c);
   }
-  // f(x): this thread's trees, then a fixed-order block sum (tree order within a thread)
-  float mx = 0.0f;
-  for (int t = tid; t < T; t += kTSThreads) mx += tree_margin<D>(xw[t], LF + t * NL);
-  mx = wave_sum(mx);
-  if (lane_id() == 0) red[wave_id()] = mx;
-  __syncthreads();
-  // phi[f] = (sum over the table's 256 columns) / n_bg: 8 threads per feature, 32 columns each
-  const int f = tid >> 3, part = tid & 7;
-  float s = 0.0f;
-  if (f < d) {
-    const float* row = ph + f * kTSThreads + part * 32;
-#pragma unroll 8
-    for (int i = 0; i < 32; ++i) s += row[i];
-  }
-  s = group_sum<8>(s);
-  if (part == 0 && f < d) phi[(int64_t)e * d + f] = s / (float)n_bg;
-  if (tid == 0) {
-    float m = base_margin;
-    for (int w = 0; w < kTSThreads / kWave; ++w) m += red[w];
-    fx_out[e] = m;
-    f0_out[e] = f0;
-  }
+  block_margin_sum<D>(xw, tc.leaf, T, base_margin, f0, red, fx_out + e, f0_out + e);
+  // phi[f] = (sum over the table's 256 columns) / n_bg
+  const float s = phi_table_sum(ph, d);
+  if ((tid & 7) == 0 && (tid >> 3) < d) phi[(int64_t)e * d + (tid >> 3)] = s / (float)n_bg;
 }
 
 }  // namespace
@@ -183,34 +135,18 @@ __global__ __launch_bounds__(kTSThreads) void treeshap_kernel(
 void launch_treeshap(const float* Xs, int ldx, int n_expl, int d, const int* feat, const float* thr,
                      const float* leaf, int ntrees, int depth, float base_margin, const uint32_t* bw, int bw_ld,
                      int n_bg, float f0, float* phi, float* fx_out, float* f0_out, hipStream_t stream) {
-  if (d < 1 || d > 30) throw std::runtime_error("treeshap: 1 <= d <= 30");
-  if (depth < 1 || depth > kTSMaxDepth) throw std::runtime_error("treeshap: depth must be in [1, 5]");
-  if (ntrees < 1 || ntrees > kTSMaxTrees) throw std::runtime_error("treeshap: 1 <= trees <= 2048");
+  check_tree_args("treeshap", d, ldx, depth, ntrees);
   if (n_bg < 1 || bw_ld < n_bg) throw std::runtime_error("treeshap: bad background");
   if (n_expl <= 0) return;
   // leaves + split features in LDS when they fit next to the phi table (<= 64 KB in total)
-  const size_t base_words = (size_t)d * kTSThreads + ntrees;
+  const size_t base_words = (size_t)d * kTreeThreads + ntrees;
   const size_t tree_words = (size_t)ntrees * (2 << depth);
   const bool lds_leaves = (base_words + tree_words) * sizeof(float) <= 65536 - 1024;
   const size_t lds = (base_words + (lds_leaves ? tree_words : 0)) * sizeof(float);
-#define FDX_TS(D_, LL)                                                                                  \
-  treeshap_kernel<D_, LL><<<n_expl, kTSThreads, lds, stream>>>(Xs, ldx, d, feat, thr, leaf, ntrees,     \
-                                                               base_margin, bw, bw_ld, n_bg, f0, phi,    \
-                                                               fx_out, f0_out)
-#define FDX_TS_D(D_)                              \
-  do {                                            \
-    if (lds_leaves) FDX_TS(D_, true);             \
-    else FDX_TS(D_, false);                       \
-  } while (0)
-  switch (depth) {
-    case 1: FDX_TS_D(1); break;
-    case 2: FDX_TS_D(2); break;
-    case 3: FDX_TS_D(3); break;
-    case 4: FDX_TS_D(4); break;
-    default: FDX_TS_D(5); break;
-  }
-#undef FDX_TS_D
-#undef FDX_TS
+  dispatch_depth(depth, lds_leaves, [&](auto D, auto in_lds) {
+    treeshap_kernel<decltype(D)::value, decltype(in_lds)::value><<<n_expl, kTreeThreads, lds, stream>>>(
+        Xs, ldx, d, feat, thr, leaf, ntrees, base_margin, bw, bw_ld, n_bg, f0, phi, fx_out, f0_out);
+  });
   check_launch("treeshap");
 }
 

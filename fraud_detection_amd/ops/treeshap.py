@@ -13,42 +13,42 @@ from .kernelshap import _check_x, _outputs
 from .native import native, ptr, stream_of
 
 
-def _device_design(expl, dev):
-    key = (str(dev),)
+def _device_design(expl, dev, kind):
+    """The explainer's arrays on the device, cached on it per (kind, device): kind "background" adds the
+    background rows' direction bits, kind "path" the child fractions and the default directions."""
+    key = (kind, str(dev))
     if expl._dev_cache is not None and expl._dev_cache[0] == key:
         return expl._dev_cache[1]
     from .scaler import stats_from_numpy
 
+    def up(a, dtype):
+        return torch.from_numpy(np.ascontiguousarray(a, dtype)).to(dev)
+
     ens = expl.ens
-    t = {
-        "feat": torch.from_numpy(np.ascontiguousarray(ens.feat, np.int32)).to(dev),
-        "thr": torch.from_numpy(np.ascontiguousarray(ens.thr, np.float32)).to(dev),
-        "leaf": torch.from_numpy(np.ascontiguousarray(ens.leaf, np.float32)).to(dev),
-        "bw": torch.from_numpy(np.ascontiguousarray(expl.bw).view(np.int32)).to(dev),
-        "stats": stats_from_numpy(expl.mean, expl.scale, device=dev),
-    }
+    t = {"feat": up(ens.feat, np.int32), "thr": up(ens.thr, np.float32), "leaf": up(ens.leaf, np.float32),
+         "stats": stats_from_numpy(expl.mean, expl.scale, device=dev)}
+    if kind == "path":
+        t["frac"] = up(expl.frac, np.float32)  # fp64 rounded once
+        t["dleft"] = up(ens.default_left, np.uint8) if getattr(ens, "has_default_left", False) else None
+    else:
+        t["bw"] = torch.from_numpy(np.ascontiguousarray(expl.bw).view(np.int32)).to(dev)
     expl._dev_cache = (key, t)
     return t
 
 
-def _device_path_design(expl, dev):
-    key = ("path", str(dev))
-    if expl._dev_cache is not None and expl._dev_cache[0] == key:
-        return expl._dev_cache[1]
-    from .scaler import stats_from_numpy
+def _explain(X, expl, kind, outs, launch, sync):
+    """What the three wrappers share after their checks: standardize X on the device, call
+    ``launch(design, Xs [E, 32], E)`` unless E = 0, and return ``outs`` (device tensors, f0 last)
+    as they are or, if ``sync``, as float64 numpy arrays with the explainer's f0."""
+    E = X.shape[0]
+    if E:
+        from .scaler import scale_cast
 
-    ens = expl.ens
-    dl = ens.default_left if getattr(ens, "has_default_left", False) else None
-    t = {
-        "feat": torch.from_numpy(np.ascontiguousarray(ens.feat, np.int32)).to(dev),
-        "thr": torch.from_numpy(np.ascontiguousarray(ens.thr, np.float32)).to(dev),
-        "leaf": torch.from_numpy(np.ascontiguousarray(ens.leaf, np.float32)).to(dev),
-        "frac": torch.from_numpy(np.ascontiguousarray(expl.frac, np.float32)).to(dev),  # fp64 rounded once
-        "dleft": torch.from_numpy(np.ascontiguousarray(dl, np.uint8)).to(dev) if dl is not None else None,
-        "stats": stats_from_numpy(expl.mean, expl.scale, device=dev),
-    }
-    expl._dev_cache = (key, t)
-    return t
+        t = _device_design(expl, X.device, kind)
+        launch(t, scale_cast(X, t["stats"], out_dtype="f32"), E)
+    if not sync:
+        return outs
+    return (*(o.cpu().numpy().astype(np.float64, copy=False) for o in outs[:-1]), float(expl.f0))
 
 
 def treeshap_path_lds_resident(d: int, n_trees: int, depth: int) -> bool:
@@ -63,25 +63,15 @@ def treeshap_path(X: torch.Tensor, expl, sync: bool = True, out=None):
     value.  Numpy if ``sync`` else device tensors (``out``: preallocated (phi, fx, f0) device
     tensors).  E = 0 launches nothing and returns empty results of these shapes."""
     _check_x(X, expl.d)
-    m = native()
-    dev = X.device
-    t = _device_path_design(expl, dev)
-    from .scaler import scale_cast
-
-    E = X.shape[0]
-    phi, fx, f0 = _outputs(E, expl.d, dev, out)
     ens = expl.ens
-    if E == 0:
-        if not sync:
-            return phi, fx, f0
-        return np.zeros((0, expl.d)), np.zeros(0), float(expl.f0)
-    Xs = scale_cast(X, t["stats"], out_dtype="f32")  # [E, 32]
-    m.treeshap_path(ptr(Xs), Xs.stride(0), E, expl.d, ptr(t["feat"]), ptr(t["thr"]), ptr(t["leaf"]), ptr(t["frac"]),
-                    ptr(t["dleft"]), ens.n_trees, ens.depth, float(ens.base_margin), float(expl.f0), ptr(phi),
-                    ptr(fx), ptr(f0), stream_of(X))
-    if not sync:
-        return phi, fx, f0
-    return phi.cpu().numpy().astype(np.float64), fx.cpu().numpy().astype(np.float64), float(expl.f0)
+    phi, fx, f0 = outs = _outputs(X.shape[0], expl.d, X.device, out)
+
+    def launch(t, Xs, E):
+        native().treeshap_path(ptr(Xs), Xs.stride(0), E, expl.d, ptr(t["feat"]), ptr(t["thr"]), ptr(t["leaf"]),
+                               ptr(t["frac"]), ptr(t["dleft"]), ens.n_trees, ens.depth, float(ens.base_margin),
+                               float(expl.f0), ptr(phi), ptr(fx), ptr(f0), stream_of(X))
+
+    return _explain(X, expl, "path", outs, launch, sync)
 
 
 def treeshap_interactions_lds_resident(d: int, n_trees: int, depth: int) -> bool:
@@ -112,11 +102,6 @@ def treeshap_interactions(X: torch.Tensor, expl, sync: bool = True, out=None, *,
     results of these shapes.  ``stream_trees`` reads the per-tree constants from L2 even where they
     fit in LDS: the same result bit for bit (the sums are integers), there for tests and timing."""
     _check_x(X, expl.d)
-    m = native()
-    dev = X.device
-    t = _device_path_design(expl, dev)
-    from .scaler import scale_cast
-
     E, d = X.shape[0], expl.d
     ens = expl.ens
     e2 = leaf_exponent(ens.leaf)
@@ -127,21 +112,16 @@ def treeshap_interactions(X: torch.Tensor, expl, sync: bool = True, out=None, *,
             raise ValueError("out = (inter [E, d, d] float64 contiguous, phi [E, d] contiguous, fx [E], f0 [E]) "
                              "device tensors")
     else:
-        inter = torch.empty((E, d, d), device=dev, dtype=torch.float64)
-        phi, fx, f0 = _outputs(E, d, dev, None)
-    if E == 0:
-        if not sync:
-            return inter, phi, fx, f0
-        return np.zeros((0, d, d)), np.zeros((0, d)), np.zeros(0), float(expl.f0)
-    Xs = scale_cast(X, t["stats"], out_dtype="f32")  # [E, 32]
-    m.treeshap_interactions(ptr(Xs), Xs.stride(0), E, d, ptr(t["feat"]), ptr(t["thr"]), ptr(t["leaf"]),
-                            ptr(t["frac"]), ptr(t["dleft"]), ens.n_trees, ens.depth, float(ens.base_margin),
-                            float(expl.f0), e2, bool(stream_trees), ptr(inter), ptr(phi), ptr(fx), ptr(f0),
-                            stream_of(X))
-    if not sync:
-        return inter, phi, fx, f0
-    return (inter.cpu().numpy(), phi.cpu().numpy().astype(np.float64), fx.cpu().numpy().astype(np.float64),
-            float(expl.f0))
+        inter = torch.empty((E, d, d), device=X.device, dtype=torch.float64)
+        phi, fx, f0 = _outputs(E, d, X.device, None)
+
+    def launch(t, Xs, E):
+        native().treeshap_interactions(ptr(Xs), Xs.stride(0), E, d, ptr(t["feat"]), ptr(t["thr"]), ptr(t["leaf"]),
+                                       ptr(t["frac"]), ptr(t["dleft"]), ens.n_trees, ens.depth,
+                                       float(ens.base_margin), float(expl.f0), e2, bool(stream_trees), ptr(inter),
+                                       ptr(phi), ptr(fx), ptr(f0), stream_of(X))
+
+    return _explain(X, expl, "path", (inter, phi, fx, f0), launch, sync)
 
 
 def treeshap(X: torch.Tensor, expl, sync: bool = True, out=None):
@@ -149,22 +129,12 @@ def treeshap(X: torch.Tensor, expl, sync: bool = True, out=None):
     margin(x) [E], f0): phi sums to margin(x) - f0, f0 = mean background margin.  Numpy if
     ``sync`` else device tensors (``out``: preallocated (phi, fx, f0) device tensors)."""
     _check_x(X, expl.d)
-    m = native()
-    dev = X.device
-    t = _device_design(expl, dev)
-    from .scaler import scale_cast
-
-    E = X.shape[0]
-    phi, fx, f0 = _outputs(E, expl.d, dev, out)
     ens = expl.ens
-    if E == 0:  # nothing to launch: empty results of the documented shapes
-        if not sync:
-            return phi, fx, f0
-        return np.zeros((0, expl.d)), np.zeros(0), float(expl.f0)
-    Xs = scale_cast(X, t["stats"], out_dtype="f32")  # [E, 32]
-    m.treeshap(ptr(Xs), Xs.stride(0), E, expl.d, ptr(t["feat"]), ptr(t["thr"]), ptr(t["leaf"]), ens.n_trees,
-               ens.depth, float(ens.base_margin), ptr(t["bw"]), expl.bw.shape[1], expl.B.shape[0], float(expl.f0),
-               ptr(phi), ptr(fx), ptr(f0), stream_of(X))
-    if not sync:
-        return phi, fx, f0
-    return phi.cpu().numpy().astype(np.float64), fx.cpu().numpy().astype(np.float64), float(expl.f0)
+    phi, fx, f0 = outs = _outputs(X.shape[0], expl.d, X.device, out)
+
+    def launch(t, Xs, E):
+        native().treeshap(ptr(Xs), Xs.stride(0), E, expl.d, ptr(t["feat"]), ptr(t["thr"]), ptr(t["leaf"]),
+                          ens.n_trees, ens.depth, float(ens.base_margin), ptr(t["bw"]), expl.bw.shape[1],
+                          expl.B.shape[0], float(expl.f0), ptr(phi), ptr(fx), ptr(f0), stream_of(X))
+
+    return _explain(X, expl, "background", outs, launch, sync)

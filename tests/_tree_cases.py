@@ -17,7 +17,7 @@ import numpy as np
 from fraud_detection_amd.ops.gbdt import TreeEnsemble
 
 U = 2.0 ** -24          # unit roundoff of fp32
-TS_THREADS = 256        # treeshap.hip kTSThreads: workgroup size = columns of the LDS phi table
+TS_THREADS = 256        # tree_explain.h kTreeThreads: workgroup size = columns of the LDS phi table
 KS_LDS_LEAVES = 8192    # kernelshap.hip kTreeLdsLeaves: leaves staged in LDS by the tree kernel
 MUTANTS = ("no_forced", "swap_w32", "le_bits")
 

@@ -16,7 +16,7 @@ import numpy as np
 import _tree_cases as TC
 
 U = TC.U
-TP_THREADS = 256   # treeshap_path.hip kTPThreads
+TP_THREADS = 256   # tree_explain.h kTreeThreads
 MUTANTS = ("no_merge", "sibling_frac", "ignore_default_left")
 
 

@@ -150,6 +150,34 @@ def test_fx_matches_the_predict_path(dev):
     TC.assert_within(fx, m, TC.fx_bound(st["fx_abs"], ens.n_trees, ens.base_margin), "fx vs predict path")
 
 
+@pytest.mark.parametrize("T", [1, 300])
+def test_margin_sum_is_shared_by_the_tree_kernels(dev, T):
+    """treeshap.hip, treeshap_path.hip and treeshap_interact.hip sum margin(x) with one routine
+    (tree_explain.h): the same fx bit for bit, at one tree and at 300, where a thread owns two
+    trees and the waves beyond the first carry partial sums.  No default_left and no NaN, so the
+    three kernels walk the same direction bits."""
+    import _tree_path_cases as PC
+    from fraud_detection_amd.models.explainers import TreePathExplainer, _margins_from_bits, path_direction_bits
+    from fraud_detection_amd.ops.treeshap import treeshap_interactions, treeshap_path
+
+    d = 4
+    Xs, Bs = TC.random_rows(d, 3, 40, 991 + T)
+    ens = PC.with_count_cover(TC.random_ensemble(d, 5, T, 990 + T), Bs)
+    assert not ens.has_default_left and not np.isnan(Xs).any()
+    Xd = torch.from_numpy(Xs).to(dev)
+    tp = TreePathExplainer(ens, np.zeros(d), np.ones(d), device=str(dev))
+    fx = {"treeshap": treeshap(Xd, _explainer(ens, Bs, dev))[1], "treeshap_path": treeshap_path(Xd, tp)[1],
+          "treeshap_interactions": treeshap_interactions(Xd, tp)[2]}
+    want = _margins_from_bits(path_direction_bits(Xs, ens), ens).astype(np.float64)
+    bound = PC.fx_bound(TC.margins64(Xs, ens)[1], T, ens.base_margin)
+    for name, got in fx.items():
+        print(f"[margin-sum] T {T} {name}: fx = {got.tolist()}")
+    assert np.array_equal(fx["treeshap"], fx["treeshap_path"])
+    assert np.array_equal(fx["treeshap"], fx["treeshap_interactions"])
+    assert np.array_equal(fx["treeshap_path"], fx["treeshap_interactions"])
+    TC.assert_within(fx["treeshap"], want, bound, f"T {T} fx vs the fp32 tree-order sum")
+
+
 def test_deterministic_and_async_form(dev):
     """A second call gives the same bits, and so does the serving engine's form: preallocated
     outputs, no synchronisation, on a stream of its own."""
