@@ -9,7 +9,9 @@ the design is implicit: every rank builds the same cached design) and the phi ro
 rank 0 (collective C8), which writes ``plots/kernelshap_values.npy``.  ``--tree``: when a GBDT was
 trained (``train_model.py --model gbdt`` -> models/xgb_model.json), explain it with interventional
 TreeSHAP (exact, margin space; shap.TreeExplainer(model, data=background) semantics) on --n rows:
-plots/treeshap_summary.png and plots/treeshap_values.npy."""
+plots/treeshap_summary.png and plots/treeshap_values.npy.  ``--pdp Amount,V14``: partial dependence
+and ICE curves of the same GBDT's margin over the model's complete threshold grid of each feature
+(``--pdp-rows`` test rows): plots/pdp_<name>.png."""
 import argparse
 import os
 
@@ -72,6 +74,10 @@ def main(argv=None):
     ap.add_argument("--kernel", action="store_true", help="also run KernelSHAP on --n rows")
     ap.add_argument("--rows", "--n", dest="n", type=int, default=1000, help="KernelSHAP rows (alias --n)")
     ap.add_argument("--tree", action="store_true", help="TreeSHAP of the GBDT model (models/xgb_model.json)")
+    ap.add_argument("--pdp", default="", metavar="NAMES",
+                    help="comma-separated features (names, Feature_<i> or indices): partial dependence and ICE "
+                         "curves of the GBDT margin, plots/pdp_<name>.png")
+    ap.add_argument("--pdp-rows", type=int, default=2000, help="rows the --pdp curves average over")
     a = ap.parse_args(argv)
     comm = None
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -126,24 +132,94 @@ def _main(a, comm):
             np.save("plots/kernelshap_values.npy", phik)
     if a.tree and lead:
         out.update(tree_explain(X_test, names, a.n))
+    if a.pdp and lead:
+        real = [str(v) for v in (art.feature_names or [])]
+        out.update(pdp_explain(X_test, real if len(real) == d else names, [w for w in a.pdp.split(",") if w],
+                               a.pdp_rows))
     print("SHAP explainability completed. Plots saved in 'plots/'.", out)
     return out
 
 
-def tree_explain(X_test, names, n) -> dict:
-    """Interventional TreeSHAP of the GBDT on the (standardized) test rows, background = 100 test
-    rows: the ensemble was trained on standardized rows, so the explainer's scaler is identity."""
+def load_gbdt(flag: str):
+    """(the GBDT ensemble of models/xgb_model.json, its path) for ``flag``, or SystemExit."""
     import json
 
-    from fraud_detection_amd.models.explainers import TreeExplainer
     from fraud_detection_amd.models.gbdt import MODEL_FILE
     from fraud_detection_amd.ops.gbdt import TreeEnsemble
 
     path = os.path.join("models", MODEL_FILE)
     if not os.path.exists(path):
-        raise SystemExit(f"--tree needs a GBDT model at {path} (train_model.py --model gbdt)")
+        raise SystemExit(f"{flag} needs a GBDT model at {path} (train_model.py --model gbdt)")
     with open(path) as f:
-        ens = TreeEnsemble.from_dict(json.load(f))
+        return TreeEnsemble.from_dict(json.load(f)), path
+
+
+def pdp_plot(pd, x, name, path, ice_lines: int = 50):
+    """Step plot of a one-feature PartialDependence: the average over thin ICE lines.  Cell 0 runs
+    from the left margin to the first edge, cell c from edge c - 1 to edge c; x: the rows' values of
+    the feature (they set the margins); the missing cell is a dashed level."""
+    e = np.asarray(pd.edges_raw[0], np.float64)
+    nv = len(e) + 1                                  # value cells (the missing cell comes after them)
+    xf = x[np.isfinite(x)]
+    lo = min(float(xf.min()) if xf.size else 0.0, float(e[0]) if e.size else 0.0)
+    hi = max(float(xf.max()) if xf.size else 1.0, float(e[-1]) if e.size else 1.0)
+    pad = 0.05 * (hi - lo) or 1.0
+    xs = np.concatenate([[lo - pad], e, [hi + pad]])
+
+    def steps(v):                                    # where="post": the last level is repeated
+        return np.concatenate([v[:nv], v[nv - 1:nv]])
+
+    fig, ax = plt.subplots(figsize=(8, 6))
+    if pd.ice is not None:
+        for row in pd.ice[np.random.default_rng(0).permutation(len(pd.ice))[:ice_lines]]:
+            ax.step(xs, steps(row), where="post", color="tab:blue", lw=0.5, alpha=0.3)
+    ax.step(xs, steps(pd.average), where="post", color="black", lw=2, label=f"average of {pd.n_rows} rows")
+    if pd.has_missing_cell:
+        ax.axhline(pd.average[-1], color="tab:red", ls="--", lw=1, label="missing")
+    ax.set_xlabel(name)
+    ax.set_ylabel("margin (log-odds)")
+    ax.legend()
+    fig.tight_layout()
+    fig.savefig(path)
+    plt.close(fig)
+
+
+def pdp_explain(X_test, names, wanted, n) -> dict:
+    """Partial dependence and ICE of the GBDT margin for the features ``wanted`` (names from
+    ``names``, "Feature_<i>" or indices) over the first n test rows: plots/pdp_<name>.png each."""
+    from fraud_detection_amd.models.explainers import TreePartialDependence
+
+    ens, path = load_gbdt("--pdp")
+    d = X_test.shape[1]
+    try:
+        te = TreePartialDependence(ens, np.zeros(d), np.ones(d))
+    except ValueError as e:
+        raise SystemExit(f"--pdp: {path} does not fit the test rows: {e}")
+    rows = X_test[:n]
+    cells = {}
+    for w in wanted:
+        if w in names:
+            f = names.index(w)
+        elif w.startswith("Feature_") and w[8:].isdigit():
+            f = int(w[8:])
+        elif w.isdigit():
+            f = int(w)
+        else:
+            raise SystemExit(f"--pdp: no feature named {w!r}")
+        if not 0 <= f < d:
+            raise SystemExit(f"--pdp: feature {w!r} is outside the {d} columns")
+        pd = te.partial_dependence(rows, f, ice=True)
+        pdp_plot(pd, rows[:, f], w, os.path.join("plots", f"pdp_{w}.png"))
+        cells[w] = int(pd.average.shape[0])
+    return {"pdp_rows": int(rows.shape[0]), "pdp_cells": cells}
+
+
+def tree_explain(X_test, names, n) -> dict:
+    """Interventional TreeSHAP of the GBDT on the (standardized) test rows, background = 100 test
+    rows: the ensemble was trained on standardized rows, so the explainer's scaler is identity."""
+    from fraud_detection_amd.models.explainers import TreeExplainer
+
+    ens, path = load_gbdt("--tree")
     d = X_test.shape[1]
     bg = X_test[np.random.default_rng(1).choice(len(X_test), min(100, len(X_test)), replace=False)]
     try:

@@ -929,6 +929,16 @@ PYBIND11_MODULE(_fdx_native, m) {
                            P<const uint8_t>(dleft), T, depth, base, kind, P<float>(ws), P<int64_t>(cover), S(s));
   });
   m.def("tree_cover_chunk_trees", &fdx::tree_cover_chunk_trees);
+  m.def("tree_pd", [](u Xs, int64_t n, int ldx, int d, u feat, u thr, u leaf, u dleft, u mask, u word_a, int cells_a,
+                      u word_b, int cells_b, int T, int depth, float base, u pd_q, u ice, u s) {
+    fdx::launch_tree_pd(P<const float>(Xs), n, ldx, d, P<const int>(feat), P<const float>(thr), P<const float>(leaf),
+                        P<const uint8_t>(dleft), P<const uint32_t>(mask), P<const uint32_t>(word_a), cells_a,
+                        P<const uint32_t>(word_b), cells_b, T, depth, base, P<int64_t>(pd_q), P<float>(ice), S(s));
+  });
+  m.attr("TREE_PD_ROWS") = fdx::tree_pd_rows_per_block();
+  m.attr("TREE_PD_CHUNK_TREES") = fdx::tree_pd_chunk_trees();
+  m.attr("TREE_PD_CELLS") = fdx::tree_pd_cells_per_block();
+  m.attr("TREE_PD_MAX_CELLS") = fdx::kTreePdMaxCells;
   m.def("kernelshap_tree", [](u Xs, int ldx, int E, int d, u feat, u thr, u leaf, int T, int depth, float base, u bw,
                               int bw_ld, int nbg, u Zm, int nS, int S_pad, int parts, u A, u Az, int link, u phi,
                               u fx, u f0, u ws, u cnt, u s) {

@@ -462,6 +462,19 @@ void launch_tree_cover(const float* X, int64_t n, int ld, int d, const int* feat
                        const float* leaf, const uint8_t* dleft, int ntrees, int depth, float base_margin,
                        int kind, float* margin_ws, int64_t* cover, hipStream_t stream);
 int tree_cover_chunk_trees(int depth);  // trees per launch: the LDS chunk
+// partial dependence / ICE of the margin (tree_pd.hip): Xs standardized [n][ldx]; mask [ntrees] the
+// heap-node bits of the nodes on the overridden features; word_a [ntrees][cells_a] (and word_b
+// [ntrees][cells_b], or null with cells_b = 1) the bits those nodes take in each cell; cell
+// ca * cells_b + cb.  pd_q int64 [cells_a * cells_b] = sum over rows of llrint((double)ice * 2^30),
+// cleared here; ice fp32 [n][cells_a * cells_b] or null.  dleft u8 [ntrees][2^depth - 1] or null.
+void launch_tree_pd(const float* Xs, int64_t n, int ldx, int d, const int* feat, const float* thr,
+                    const float* leaf, const uint8_t* dleft, const uint32_t* mask, const uint32_t* word_a,
+                    int cells_a, const uint32_t* word_b, int cells_b, int ntrees, int depth, float base_margin,
+                    int64_t* pd_q, float* ice, hipStream_t stream);
+int tree_pd_rows_per_block();   // rows of one workgroup
+int tree_pd_chunk_trees();      // trees per LDS chunk
+int tree_pd_cells_per_block();  // cells of one workgroup (grid y runs over cell tiles)
+constexpr int kTreePdMaxCells = 65536;
 void launch_kernelshap_tree(const float* Xs, int ldx, int n_expl, int d, const int* feat, const float* thr,
                             const float* leaf, int ntrees, int depth, float base_margin, const uint32_t* bw,
                             int bw_ld, int n_bg, const uint32_t* Zm, int S, int S_pad, int parts,

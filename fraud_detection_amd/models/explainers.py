@@ -33,6 +33,9 @@ XGBoost model):
     in the model (treeshap_path.hip): exact, no background, NaN follows the learned default
     direction -- xgboost's pred_contribs; and the SHAP interaction values of the same game
     (treeshap_interact.hip) -- pred_interactions, shap_interaction_values;
+  * ``TreePartialDependence`` -- the global counterpart: partial dependence and ICE curves of the
+    GBDT margin over the complete threshold grid of one feature or a pair (tree_pd.hip), brute
+    (exact integer means over the rows) or by recursion over the stored node covers;
   * ``FunctionKernelExplainer`` -- any callable on device tensors (e.g. a torch model): masked rows
     are built in chunks on the device, the model is called on them, and the shared WLS operator
     projects the coalition values.
@@ -44,6 +47,7 @@ import functools
 import itertools
 import math
 import time
+from dataclasses import dataclass
 
 import numpy as np
 import torch
@@ -674,6 +678,11 @@ def treeshap_interactions_reference(Xs: np.ndarray, ens) -> tuple:
     return inter, phi, fx, path_expected_value(ens, frac)
 
 
+def _no_cover_message(who: str) -> str:
+    return (f"{who} needs the model's node covers: compute them with node_cover "
+            "(GBDTClassifier.compute_cover, fit(..., record_cover=True) or train --gbdt-cover)")
+
+
 class TreePathExplainer:
     """Path-dependent TreeSHAP of a tree ensemble (ops/gbdt.TreeEnsemble on standardized rows) over
     RAW inputs, in margin (log-odds) space -- xgboost's predict(pred_contribs=True) and
@@ -686,8 +695,7 @@ class TreePathExplainer:
 
     def __init__(self, ens, mean, scale, device="auto"):
         if getattr(ens, "cover", None) is None:
-            raise ValueError("TreePathExplainer needs the model's node covers: compute them with node_cover "
-                             "(GBDTClassifier.compute_cover, fit(..., record_cover=True) or train --gbdt-cover)")
+            raise ValueError(_no_cover_message("TreePathExplainer"))
         if not 1 <= ens.depth <= 5:
             raise ValueError("path TreeSHAP supports depth 1..5 (the reference trains max_depth=5)")
         if not 1 <= ens.n_trees <= 2048:
@@ -742,6 +750,117 @@ class TreePathExplainer:
         if X.shape[0] == 0:
             return np.zeros((0, self.d, self.d)), np.zeros((0, self.d)), np.zeros(0), self.f0
         return treeshap_interactions_reference(_standardize(X, self.mean, self.scale), self.ens)
+
+
+def partial_dependence_recursion(ens, features) -> np.ndarray:
+    """float64 [C]: sklearn's ``method="recursion"`` on the stored node covers, no rows needed --
+    the path-dependent game's v({f}) per cell.  rec[c] = base_margin + sum_t sum_leaves leaf * prod
+    over the leaf's path of (path_fractions of the child taken) at nodes not on the features and (1
+    if the child taken is the side cell c goes, else 0) at nodes on them.  A pair's cells are
+    flattened as ca * C_b + cb.  ValueError without covers (path_fractions)."""
+    from ..ops.pdp import pd_design
+
+    frac = path_fractions(ens)
+    _, _, mask, words = pd_design(ens, features)
+    T, D = ens.n_trees, ens.depth
+    W = words[0] if len(words) == 1 else (words[0][:, :, None] | words[1][:, None, :]).reshape(T, -1)
+    rec = np.full(W.shape[1], float(ens.base_margin))
+    for l in range(1 << D):
+        heap = (1 << D) + l
+        w = np.ones(W.shape)
+        for j in range(D):
+            k, c = heap >> (D - j), heap >> (D - j - 1)
+            on = ((mask >> np.uint32(k)) & 1).astype(bool)
+            side = ((W >> np.uint32(k)) & 1) == (c & 1)
+            w *= np.where(on[:, None], side, frac[:, c][:, None])
+        rec += (w * ens.leaf[:, l].astype(np.float64)[:, None]).sum(0)
+    return rec
+
+
+@dataclass
+class PartialDependence:
+    """What TreePartialDependence.partial_dependence returns.  ``edges[i]`` / ``edges_raw[i]``: the
+    ascending thresholds of ``features[i]`` in standardized / raw units; value cell 0 lies below the
+    first edge and cell c >= 1 is [edge c-1, edge c).  ``has_missing_cell``: one more cell, last on
+    every axis, holds "the feature is missing".  ``average`` [C_a] or [C_a, C_b] in log-odds;
+    ``pd_q`` the exact int64 sums behind it (brute: average = pd_q / 2^30 / n_rows; None for
+    recursion); ``ice`` float32 [n, C_a] or [n, C_a, C_b] where asked for."""
+    features: tuple
+    edges: tuple
+    edges_raw: tuple
+    has_missing_cell: bool
+    average: np.ndarray
+    pd_q: np.ndarray | None
+    ice: np.ndarray | None
+    n_rows: int
+    method: str
+
+
+class TreePartialDependence:
+    """Partial dependence and ICE curves of a tree ensemble's margin (ops/gbdt.TreeEnsemble on
+    standardized rows) over RAW inputs -- sklearn.inspection.partial_dependence for this family, the
+    global counterpart of the tree explainers.  The model is piecewise constant in a feature, so the
+    COMPLETE curve has one value per cell between the ensemble's distinct thresholds on it (no grid
+    resolution to choose), plus a "missing" cell where the model learned default directions.
+
+    ``method="brute"``: every row's margin with the feature placed in the cell and everything else as
+    observed (the interventional v({f}); a NaN elsewhere follows default_left), averaged over the
+    rows as an exact int64 sum of llrint(margin * 2^30) -- bitwise reproducible; ICE is bit for bit
+    ``predict_margin`` on the modified rows (csrc/kernels/tree_pd.hip on a GPU explainer, the numpy
+    oracle on CPU).  ``method="recursion"``: the path-dependent v({f}) from the stored node covers,
+    no rows, fp64 on the host.  The two agree at depth 1 (count covers over the same NaN-free rows)
+    and differ wherever features interact or are correlated, as in sklearn.  Limits: depth 1..5, at
+    most 2048 trees and 30 features, one feature or a pair, at most 65,536 cells."""
+
+    def __init__(self, ens, mean, scale, device="auto"):
+        from ..ops import reference_gbdt as R
+
+        self.mean = np.asarray(mean, np.float64)
+        self.scale = np.asarray(scale, np.float64)
+        self.d = len(self.mean)
+        if self.d != ens.n_features:
+            raise ValueError(f"model has {ens.n_features} features, the scaler {self.d}")
+        R.pd_check(ens, 0, 0)
+        _check_tree_features(ens, self.d)
+        self.ens = ens
+        self.device = torch.device("cuda", 0) if (device == "auto" and torch.cuda.is_available()) else torch.device(
+            "cpu" if device == "auto" else device)
+        self._dev_cache = None
+
+    def grid(self, f: int):
+        """(edges float32 in standardized units, edges float64 in raw units) of feature f."""
+        from ..ops.reference_gbdt import pd_grid
+
+        e = pd_grid(self.ens, f)
+        return e, e.astype(np.float64) * self.scale[int(f)] + self.mean[int(f)]
+
+    def partial_dependence(self, X=None, features=0, method: str = "brute", ice: bool = False) -> PartialDependence:
+        from ..ops import reference_gbdt as R
+
+        if method not in ("brute", "recursion"):
+            raise ValueError('method must be "brute" or "recursion"')
+        fs = R.pd_features(self.ens, features)
+        grids = [self.grid(f) for f in fs]
+        shape = tuple(len(R.pd_cells(self.ens, f)[0]) for f in fs)
+        common = dict(features=fs, edges=tuple(g[0] for g in grids), edges_raw=tuple(g[1] for g in grids),
+                      has_missing_cell=bool(self.ens.has_default_left), method=method)
+        if method == "recursion":
+            if ice:
+                raise ValueError("recursion has no rows and no ICE curves")
+            if getattr(self.ens, "cover", None) is None:
+                raise ValueError(_no_cover_message("TreePartialDependence"))
+            R.pd_check(self.ens, fs, 0)
+            return PartialDependence(average=partial_dependence_recursion(self.ens, fs).reshape(shape), pd_q=None,
+                                     ice=None, n_rows=0, **common)
+        from ..ops.pdp import partial_dependence
+
+        X = np.ascontiguousarray(X, np.float32)
+        if X.ndim != 2 or X.shape[0] < 1:
+            raise ValueError("brute partial dependence needs at least one row")
+        q, ic = partial_dependence(torch.from_numpy(X).to(self.device), self, fs, ice=ice)
+        n = X.shape[0]
+        return PartialDependence(average=(q.astype(np.float64) / R.PD_SCALE / n).reshape(shape), pd_q=q.reshape(shape),
+                                 ice=None if ic is None else ic.reshape((n,) + shape), n_rows=n, **common)
 
 
 class FunctionKernelExplainer:

@@ -109,6 +109,7 @@ class GBDTClassifier:
         st = dict(self.__dict__)
         st["_dens"] = None
         st.pop("_pexpl", None)
+        st.pop("_pdexpl", None)
         st["params"] = dict(self.params.__dict__)
         return st
 
@@ -286,6 +287,35 @@ class GBDTClassifier:
             self._pexpl = cache
         Xh = X.detach().cpu().numpy() if isinstance(X, torch.Tensor) else np.asarray(X)
         return cache[1], np.ascontiguousarray(Xh, np.float32)
+
+    def partial_dependence(self, X, features, method: str = "brute", kind: str = "average", iteration_range=None):
+        """sklearn.inspection.partial_dependence for this model, on the margin (log-odds) and over the
+        COMPLETE grid: one cell per interval between the model's thresholds on the feature (an int, or
+        a pair of ints for a 2-D surface), plus a "missing" cell on a ``missing_policy="learn"`` model.
+        ``method="brute"`` averages the rows X with the feature placed in each cell (exact integer
+        sums, bitwise reproducible); ``"recursion"`` needs the node covers instead of rows (X may be
+        None) and differs from brute wherever features interact.  ``kind``: "average", or
+        "individual" / "both", which also return the ICE curves (float32 [n, cells], bit for bit
+        ``predict_margin`` of the modified rows; the average comes with them either way).  Returns a
+        ``models.explainers.PartialDependence``; ``iteration_range=(0, k)`` uses the first k trees."""
+        self._check()
+        if kind not in ("average", "individual", "both"):
+            raise ValueError('kind must be "average", "individual" or "both"')
+        from .explainers import TreePartialDependence
+
+        k = self._n_trees(iteration_range)
+        k = self.ensemble.n_trees if k is None else k
+        dev = self._dev(X) if X is not None else torch.device("cpu")
+        cache = getattr(self, "_pdexpl", None)
+        key = (k, str(dev), id(self.ensemble))
+        if cache is None or cache[0] != key:
+            d = self.ensemble.n_features
+            cache = (key, TreePartialDependence(self.ensemble.head(k), np.zeros(d), np.ones(d), device=str(dev)))
+            self._pdexpl = cache
+        if method == "recursion":
+            return cache[1].partial_dependence(None, features, "recursion", ice=kind != "average")
+        Xh = X.detach().cpu().numpy() if isinstance(X, torch.Tensor) else np.asarray(X)
+        return cache[1].partial_dependence(Xh, features, method, ice=kind != "average")
 
     def feature_importance(self, kind: str = "gain") -> np.ndarray:
         """``TreeEnsemble.feature_importance``: "gain", "weight", "total_gain", "cover", "total_cover"."""

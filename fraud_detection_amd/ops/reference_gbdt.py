@@ -775,3 +775,99 @@ def node_cover(X: np.ndarray, feat: np.ndarray, thr: np.ndarray, leaf: np.ndarra
         for k in range(nl - 1, 0, -1):
             out[t, k] = out[t, 2 * k] + out[t, 2 * k + 1]
     return out
+
+
+# ---- partial dependence / ICE of the margin ---------------------------------------------------------
+# The model is piecewise constant, so the complete curve of feature f has one value per CELL: the
+# intervals between the ensemble's distinct thresholds on f (models/explainers.py
+# TreePartialDependence has the definitions; csrc/kernels/tree_pd.hip is the device form).
+PD_SCALE = float(2 ** 30)  # fixed point of a row's margin in the partial-dependence sums
+PD_MAX_CELLS = 65536
+
+
+def pd_grid(ens, f: int) -> np.ndarray:
+    """E_f, float32 ascending: the distinct thresholds of the nodes that split on feature f, -inf (a
+    "missing rows only" split, bin -1) dropped.  K_f = len(E_f) edges make K_f + 1 value cells."""
+    f = int(f)
+    if not 0 <= f < ens.n_features:
+        raise ValueError(f"feature {f} out of range [0, {ens.n_features})")
+    thr = np.asarray(ens.thr, np.float32)[np.asarray(ens.feat) == f]
+    return np.unique(thr[thr != -np.inf])
+
+
+def pd_cells(ens, f: int):
+    """(representatives float32 [C], has_missing): cell 0 is -inf (below every edge), cell c >= 1 the
+    edge E_f[c - 1] (standing for [E_f[c-1], E_f[c])), and where the model has learned default
+    directions one last cell NaN, "missing"."""
+    reps = np.concatenate([np.array([-np.inf], np.float32), pd_grid(ens, f)])
+    if ens.has_default_left:
+        reps = np.concatenate([reps, np.array([np.nan], np.float32)])
+    return reps, bool(ens.has_default_left)
+
+
+def pd_features(ens, features) -> tuple:
+    """``features`` (an int or a pair of distinct ints) as a checked tuple."""
+    fs = (int(features),) if np.isscalar(features) else tuple(int(v) for v in features)
+    if len(fs) not in (1, 2):
+        raise ValueError("partial dependence takes one feature or a pair")
+    for f in fs:
+        if not 0 <= f < ens.n_features:
+            raise ValueError(f"feature {f} out of range [0, {ens.n_features})")
+    if len(fs) == 2 and fs[0] == fs[1]:
+        raise ValueError("the two features of a pair must differ")
+    return fs
+
+
+def pd_check(ens, features, n: int):
+    """(features tuple, per-feature representatives, has_missing) after the family's limits, the cell
+    cap and the int64 guard: with Mb = |base_margin| + sum_t max |leaf_t| a sum of n rows stays below
+    2^63 when n (Mb + 1) 2^30 < 2^63."""
+    if not 1 <= ens.depth <= 5:
+        raise ValueError("partial dependence supports depth 1..5 (the reference trains max_depth=5)")
+    if not 1 <= ens.n_trees <= 2048:
+        raise ValueError("partial dependence supports 1..2048 trees")
+    if ens.n_features > 30:
+        raise ValueError(f"tree explainers support at most 30 features, the model has {ens.n_features}")
+    fs = pd_features(ens, features)
+    cells = [pd_cells(ens, f) for f in fs]
+    total = int(np.prod([len(r) for r, _ in cells]))
+    if total > PD_MAX_CELLS:
+        raise ValueError(f"{total} cells: at most {PD_MAX_CELLS} (shorten the model with iteration_range or take "
+                         "one feature)")
+    leaf = np.abs(np.asarray(ens.leaf, np.float64))
+    if not np.all(np.isfinite(leaf)):
+        raise ValueError("partial dependence needs finite leaf values")
+    mb = abs(float(ens.base_margin)) + float(leaf.max(1).sum())
+    if float(n) * (mb + 1.0) * PD_SCALE >= 2.0 ** 63:
+        raise ValueError(f"{n} rows of margins up to {mb:.3g} would overflow the int64 sums")
+    return fs, [r for r, _ in cells], bool(ens.has_default_left)
+
+
+def partial_dependence_reference(Xs: np.ndarray, ens, features, ice: bool = True):
+    """The oracle: ICE and brute partial dependence of the margin on STANDARDIZED rows Xs [n, d] by
+    predict_margin on copies of Xs whose column f holds the cell's representative (NaN for the missing
+    cell).  Returns (pd_q int64 [C], ice float32 [n, C] or None); a pair's cells are flattened as
+    ca * C_b + cb; pd_q[c] = sum_i rint((double)ice[i, c] * 2^30)."""
+    Xs = np.asarray(Xs, np.float32)
+    if Xs.ndim != 2 or Xs.shape[1] != ens.n_features:
+        raise ValueError(f"model has {ens.n_features} features, X has shape {Xs.shape}")
+    fs, reps, _ = pd_check(ens, features, Xs.shape[0])
+    dl = ens.default_left if ens.has_default_left else None
+    n, d = Xs.shape
+    pair = len(fs) == 2
+    cb = len(reps[1]) if pair else 1
+    va = np.repeat(reps[0], cb)                       # the flattened cell's value of the first feature
+    vb = np.tile(reps[1], len(reps[0])) if pair else None
+    C = len(va)
+    out = np.empty((n, C), np.float32)
+    step = max(1, (1 << 20) // max(n, 1))             # cells per predict_margin call: <= 2^20 rows at a time
+    for c0 in range(0, C, step):
+        c1 = min(C, c0 + step)
+        Xm = np.repeat(Xs[None], c1 - c0, 0)          # [cells, n, d]
+        Xm[:, :, fs[0]] = va[c0:c1, None]
+        if pair:
+            Xm[:, :, fs[1]] = vb[c0:c1, None]
+        m = predict_margin(Xm.reshape(-1, d), ens.feat, ens.thr, ens.leaf, ens.depth, ens.base_margin, dl)
+        out[:, c0:c1] = m.reshape(c1 - c0, n).T
+    pd_q = np.rint(out.astype(np.float64) * PD_SCALE).astype(np.int64).sum(0)
+    return pd_q, (out if ice else None)
