@@ -939,6 +939,16 @@ PYBIND11_MODULE(_fdx_native, m) {
   m.attr("TREE_PD_CHUNK_TREES") = fdx::tree_pd_chunk_trees();
   m.attr("TREE_PD_CELLS") = fdx::tree_pd_cells_per_block();
   m.attr("TREE_PD_MAX_CELLS") = fdx::kTreePdMaxCells;
+  m.def("tree_perm", [](u Xs, int64_t n, int ldx, int d, u feat, u thr, u leaf, u dleft, u fmask, int T, int depth,
+                        float base, u col_feat, u col_rep, int ncols, uint32_t seed, u out, u s) {
+    fdx::launch_tree_perm(P<const float>(Xs), n, ldx, d, P<const int>(feat), P<const float>(thr), P<const float>(leaf),
+                          P<const uint8_t>(dleft), P<const uint32_t>(fmask), T, depth, base, P<const int>(col_feat),
+                          P<const int>(col_rep), ncols, seed, P<float>(out), S(s));
+  });
+  m.attr("TREE_PERM_ROWS") = fdx::tree_perm_rows_per_block();
+  m.attr("TREE_PERM_CHUNK_TREES") = fdx::tree_perm_chunk_trees();
+  m.attr("TREE_PERM_COLS") = fdx::tree_perm_cols_per_block();
+  m.attr("TREE_PERM_MAX_COLS") = fdx::kTreePermMaxCols;
   m.def("kernelshap_tree", [](u Xs, int ldx, int E, int d, u feat, u thr, u leaf, int T, int depth, float base, u bw,
                               int bw_ld, int nbg, u Zm, int nS, int S_pad, int parts, u A, u Az, int link, u phi,
                               u fx, u f0, u ws, u cnt, u s) {

@@ -475,6 +475,20 @@ int tree_pd_rows_per_block();   // rows of one workgroup
 int tree_pd_chunk_trees();      // trees per LDS chunk
 int tree_pd_cells_per_block();  // cells of one workgroup (grid y runs over cell tiles)
 constexpr int kTreePdMaxCells = 65536;
+// permuted margins for permutation importance (tree_perm.hip): out fp32 [ncols][n], out[j][i] the
+// margin of row i of Xs [n][ldx] with feature col_feat[j] taken from row donor(i) of the keyed
+// Feistel permutation (seed, stream 32 col_rep[j] + col_feat[j]; feistel_perm.h) and everything else
+// as observed; col_feat[j] = -1: the unpermuted margin.  fmask u32 [ntrees][32]: per feature, the
+// heap-node bits of the tree's nodes that split on it.  dleft u8 [ntrees][2^depth - 1] or null.
+// col_feat / col_rep are device arrays [ncols].
+void launch_tree_perm(const float* Xs, int64_t n, int ldx, int d, const int* feat, const float* thr,
+                      const float* leaf, const uint8_t* dleft, const uint32_t* fmask, int ntrees, int depth,
+                      float base_margin, const int* col_feat, const int* col_rep, int ncols, uint32_t seed,
+                      float* out, hipStream_t stream);
+int tree_perm_rows_per_block();  // rows of one workgroup
+int tree_perm_chunk_trees();     // trees per LDS chunk
+int tree_perm_cols_per_block();  // columns of one workgroup (grid y runs over column tiles)
+constexpr int kTreePermMaxCols = 1 << 20;
 void launch_kernelshap_tree(const float* Xs, int ldx, int n_expl, int d, const int* feat, const float* thr,
                             const float* leaf, int ntrees, int depth, float base_margin, const uint32_t* bw,
                             int bw_ld, int n_bg, const uint32_t* Zm, int S, int S_pad, int parts,

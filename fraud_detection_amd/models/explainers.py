@@ -863,6 +863,97 @@ class TreePartialDependence:
                                  ice=None if ic is None else ic.reshape((n,) + shape), n_rows=n, **common)
 
 
+@dataclass
+class PermutationImportance:
+    """What TreePermutationImportance.permutation_importance returns (the fields of sklearn's
+    ``permutation_importance`` Bunch and the exact integers behind them).  ``raw`` int64 [F, R] and
+    ``baseline_raw``: the metric kernel's integer per permuted column and for the observed rows
+    ("auc": twice_pairs, "aucpr": ap_q, "logloss": loss_q).  ``scores`` / ``baseline_score``: the
+    metric, higher is better -- AUC = raw / (2 P N), average precision = raw / 2^30 / P, negative
+    log-loss = -raw / 2^30 / n.  ``importances`` = baseline_score - scores, float64 [F, R];
+    ``importances_mean`` / ``importances_std`` over the repeats (ddof = 0, as sklearn)."""
+    features: tuple
+    scoring: str
+    n_repeats: int
+    seed: int
+    baseline_raw: int
+    raw: np.ndarray
+    baseline_score: float
+    scores: np.ndarray
+    importances: np.ndarray
+    importances_mean: np.ndarray
+    importances_std: np.ndarray
+
+
+class TreePermutationImportance:
+    """Permutation feature importance of a tree ensemble (ops/gbdt.TreeEnsemble on standardized rows)
+    over RAW inputs -- sklearn.inspection.permutation_importance for this family: how much the
+    held-out metric drops when one feature carries no information.
+
+    Column (feature f, repeat r) gives row i the value of feature f of row donor(i) and leaves the
+    rest of the row as observed; donor is a keyed Feistel permutation of the rows
+    (ops/reference_gbdt.permutation_donors) with the column id 32 r + f, so repeat r of feature f is
+    the same permutation whatever ``n_repeats`` and ``features`` are.  The column's margins are bit
+    for bit ``predict_margin`` on the explicitly permuted rows (a NaN, the row's own or the donor's,
+    follows default_left) and its score is the metric kernel's exact integer, so results are bitwise
+    reproducible and equal between the device (csrc/kernels/tree_perm.hip and the metric kernels,
+    one read-back) and the CPU (the numpy oracle).  ``scoring``: "auc", "aucpr" (sklearn's average
+    precision over tie groups) or "logloss" (sklearn's neg_log_loss, log-loss per row capped at
+    -ln 1e-16).  Limits: depth 1..5, at most 2048 trees and 30 features, at most 2^27 rows, labels
+    0/1 with both classes for "auc" / "aucpr".  Out of scope: sample weights, data-parallel
+    evaluation, the logistic model, other scorers, ``max_samples``."""
+
+    def __init__(self, ens, mean, scale, device="auto"):
+        from ..ops import reference_gbdt as R
+
+        self.mean = np.asarray(mean, np.float64)
+        self.scale = np.asarray(scale, np.float64)
+        self.d = len(self.mean)
+        if self.d != ens.n_features:
+            raise ValueError(f"model has {ens.n_features} features, the scaler {self.d}")
+        R.perm_check(ens, None, 1, 0)
+        _check_tree_features(ens, self.d)
+        self.ens = ens
+        self.device = torch.device("cuda", 0) if (device == "auto" and torch.cuda.is_available()) else torch.device(
+            "cpu" if device == "auto" else device)
+        self._dev_cache = None
+
+    def permutation_importance(self, X, y, scoring: str = "auc", n_repeats: int = 5, seed: int = 0, features=None,
+                               max_bytes: int | None = None) -> PermutationImportance:
+        """X [n, d] raw rows and y [n] 0/1 labels, numpy arrays or torch tensors (moved to the
+        explainer's device).  ``features``: the feature indices to permute (None: all).
+        ``max_bytes``: the cap of the device margin buffer (ops/perm_importance.permutation_scores)."""
+        from ..ops import reference_gbdt as R
+        from ..ops.perm_importance import DEFAULT_MAX_BYTES, SCORINGS, permutation_scores
+
+        if scoring not in SCORINGS:
+            raise ValueError(f"scoring must be one of {SCORINGS}, not {scoring!r}")
+        fs = R.perm_check(self.ens, features, n_repeats, seed)
+        Xt = X if isinstance(X, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(X, np.float32))
+        yt = y if isinstance(y, torch.Tensor) else torch.from_numpy(np.asarray(y))
+        if Xt.dim() != 2 or Xt.shape[0] < 1:
+            raise ValueError("permutation importance needs at least one row")
+        n = int(Xt.shape[0])
+        if yt.dim() != 1 or yt.shape[0] != n:
+            raise ValueError(f"y must hold one label per row of X ({n}), got shape {tuple(yt.shape)}")
+        Xt = Xt.to(self.device, torch.float32)
+        yt = (yt.to(self.device) != 0).to(torch.uint8)
+        raw, base_raw, P = permutation_scores(Xt, yt, self, fs, scoring, int(n_repeats), int(seed),
+                                              DEFAULT_MAX_BYTES if max_bytes is None else int(max_bytes))
+        if scoring == "auc":
+            to_score = lambda q: q / (2.0 * P * (n - P))  # noqa: E731
+        elif scoring == "aucpr":
+            to_score = lambda q: q / 2.0 ** 30 / P  # noqa: E731
+        else:
+            to_score = lambda q: -q / R.LOSS_SCALE / n  # noqa: E731
+        scores = to_score(raw.astype(np.float64))
+        base = float(to_score(float(base_raw)))
+        imp = base - scores
+        return PermutationImportance(features=fs, scoring=scoring, n_repeats=int(n_repeats), seed=int(seed),
+                                     baseline_raw=int(base_raw), raw=raw, baseline_score=base, scores=scores,
+                                     importances=imp, importances_mean=imp.mean(1), importances_std=imp.std(1))
+
+
 class FunctionKernelExplainer:
     """KernelSHAP of any model given as ``fn(rows: Tensor[N, d]) -> Tensor[N]`` (the model output
     in the link's input space: probabilities for identity / logit, log-odds for logit_model).

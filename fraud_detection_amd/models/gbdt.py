@@ -110,6 +110,7 @@ class GBDTClassifier:
         st["_dens"] = None
         st.pop("_pexpl", None)
         st.pop("_pdexpl", None)
+        st.pop("_piexpl", None)
         st["params"] = dict(self.params.__dict__)
         return st
 
@@ -316,6 +317,30 @@ class GBDTClassifier:
             return cache[1].partial_dependence(None, features, "recursion", ice=kind != "average")
         Xh = X.detach().cpu().numpy() if isinstance(X, torch.Tensor) else np.asarray(X)
         return cache[1].partial_dependence(Xh, features, method, ice=kind != "average")
+
+    def permutation_importance(self, X, y, scoring: str = "auc", n_repeats: int = 5, seed: int = 0, features=None,
+                               iteration_range=None):
+        """sklearn.inspection.permutation_importance for this model: the drop of the metric on the
+        rows (X, y) -- held-out rows, untouched by resampling or reweighting -- when one feature is
+        permuted among them, ``n_repeats`` times per feature.  ``scoring``: "auc", "aucpr" (average
+        precision) or "logloss" (negative log-loss), higher is better; ``features``: the feature
+        indices to permute (None: all); ``seed``: an integer in [0, 2^32).  Margins and scores are
+        exact (bit for bit ``predict_margin`` on the permuted rows, integer metric sums), so CPU and
+        device agree exactly.  Returns a ``models.explainers.PermutationImportance``;
+        ``iteration_range=(0, k)`` uses the first k trees."""
+        self._check()
+        from .explainers import TreePermutationImportance
+
+        k = self._n_trees(iteration_range)
+        k = self.ensemble.n_trees if k is None else k
+        dev = self._dev(X)
+        cache = getattr(self, "_piexpl", None)
+        key = (k, str(dev), id(self.ensemble))
+        if cache is None or cache[0] != key:
+            d = self.ensemble.n_features
+            cache = (key, TreePermutationImportance(self.ensemble.head(k), np.zeros(d), np.ones(d), device=str(dev)))
+            self._piexpl = cache
+        return cache[1].permutation_importance(X, y, scoring, n_repeats, seed, features)
 
     def feature_importance(self, kind: str = "gain") -> np.ndarray:
         """``TreeEnsemble.feature_importance``: "gain", "weight", "total_gain", "cover", "total_cover"."""

@@ -871,3 +871,99 @@ def partial_dependence_reference(Xs: np.ndarray, ens, features, ice: bool = True
         out[:, c0:c1] = m.reshape(c1 - c0, n).T
     pd_q = np.rint(out.astype(np.float64) * PD_SCALE).astype(np.int64).sum(0)
     return pd_q, (out if ice else None)
+
+
+# ---- permutation feature importance -----------------------------------------------------------------
+# Column (feature f, repeat r) gives row i the value of feature f of row donors[i] and leaves the
+# rest of the row as observed (models/explainers.py TreePermutationImportance has the definitions;
+# csrc/kernels/feistel_perm.h and tree_perm.hip are the device form).
+def _fmix32(x):
+    x = np.asarray(x, dtype=np.uint32).copy()
+    x ^= x >> np.uint32(16)
+    x *= np.uint32(0x85EBCA6B)
+    x ^= x >> np.uint32(13)
+    x *= np.uint32(0xC2B2AE35)
+    x ^= x >> np.uint32(16)
+    return x
+
+
+def permutation_donors(n: int, seed: int, f: int, r: int) -> np.ndarray:
+    """int64 [n]: the permutation of the rows that column (feature f, repeat r) reads feature f
+    through.  A keyed Feistel bijection with cycle walking (the construction of ops/split's class
+    permutation on the domain [0, n)): 4 rounds over half-words of h = (b + 1) >> 1 bits, 2^b >= n and
+    b >= 2, fmix32 as the round function, applied again while the value is >= n; keys
+    key[k] = fmix32(seed ^ fmix32(0x9E3779B9 (2 c + 1) + k)) with the column id c = 32 r + f.  So
+    repeat r of feature f is the same permutation whatever else is asked for.  ``seed`` is an integer
+    in [0, 2^32)."""
+    n, seed, f, r = int(n), int(seed), int(f), int(r)
+    if n < 0:
+        raise ValueError("negative row count")
+    if not 0 <= seed < 2 ** 32:
+        raise ValueError("seed must be an integer in [0, 2^32)")
+    if not 0 <= f < 32 or r < 0:
+        raise ValueError("column (f, r) needs 0 <= f < 32 and r >= 0")
+    c = 32 * r + f
+    b = 2
+    while b < 64 and (1 << b) < n:
+        b += 1
+    h = (b + 1) >> 1
+    mask = np.uint64((1 << h) - 1)
+    with np.errstate(over="ignore"):
+        keys = [int(_fmix32(np.uint32(seed) ^ _fmix32(np.uint32((0x9E3779B9 * (2 * c + 1) + k) & 0xFFFFFFFF))))
+                for k in range(4)]
+        x = np.arange(n, dtype=np.uint64)
+        todo = np.ones(n, bool)
+        while todo.any():
+            xs = x[todo]
+            L, Rh = xs >> np.uint64(h), xs & mask
+            for kv in keys:
+                g = _fmix32((Rh ^ np.uint64(kv)).astype(np.uint32)).astype(np.uint64) & mask
+                L, Rh = Rh, L ^ g
+            xs = (L << np.uint64(h)) | Rh
+            x[todo] = xs
+            todo[todo] = xs >= np.uint64(n)
+    return x.astype(np.int64)
+
+
+def perm_check(ens, features, n_repeats: int, seed: int) -> tuple:
+    """The checked feature tuple of a permutation-importance call (None: every feature) after the
+    family's limits: depth 1..5, 1..2048 trees, at most 30 features."""
+    if not 1 <= ens.depth <= 5:
+        raise ValueError("permutation importance supports depth 1..5 (the reference trains max_depth=5)")
+    if not 1 <= ens.n_trees <= 2048:
+        raise ValueError("permutation importance supports 1..2048 trees")
+    d = ens.n_features
+    if d > 30:
+        raise ValueError(f"tree explainers support at most 30 features, the model has {d}")
+    if int(n_repeats) < 1:
+        raise ValueError("n_repeats must be at least 1")
+    if not 0 <= int(seed) < 2 ** 32:
+        raise ValueError("seed must be an integer in [0, 2^32)")
+    fs = tuple(range(d)) if features is None else tuple(int(v) for v in np.atleast_1d(np.asarray(features)))
+    for f in fs:
+        if not 0 <= f < d:
+            raise ValueError(f"feature {f} out of range [0, {d})")
+    if len(set(fs)) != len(fs):
+        raise ValueError("a feature is listed twice")
+    if len(fs) < 1:
+        raise ValueError("no feature to permute")
+    return fs
+
+
+def permuted_margins_reference(Xs: np.ndarray, ens, features, n_repeats: int, seed: int):
+    """The oracle: (float32 [F, R, n], float32 [n]) -- predict_margin on explicit copies of the
+    STANDARDIZED rows Xs [n, d] whose column f is Xs[permutation_donors(n, seed, f, r), f], and
+    predict_margin of Xs itself (the baseline)."""
+    Xs = np.asarray(Xs, np.float32)
+    if Xs.ndim != 2 or Xs.shape[1] != ens.n_features:
+        raise ValueError(f"model has {ens.n_features} features, X has shape {Xs.shape}")
+    fs = perm_check(ens, features, n_repeats, seed)
+    dl = ens.default_left if ens.has_default_left else None
+    n = Xs.shape[0]
+    out = np.empty((len(fs), int(n_repeats), n), np.float32)
+    for i, f in enumerate(fs):
+        for r in range(int(n_repeats)):
+            Xm = Xs.copy()
+            Xm[:, f] = Xs[permutation_donors(n, seed, f, r), f]
+            out[i, r] = predict_margin(Xm, ens.feat, ens.thr, ens.leaf, ens.depth, ens.base_margin, dl)
+    return out, predict_margin(Xs, ens.feat, ens.thr, ens.leaf, ens.depth, ens.base_margin, dl)
