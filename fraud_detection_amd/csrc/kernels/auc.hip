@@ -690,6 +690,8 @@ void launch_sort_chunks(float* pos, int64_t npos_cap, const unsigned long long* 
 void launch_auc_count(const float* scores, const uint8_t* labels, int64_t n, const float* pos,
                       const unsigned long long* counter, int chunk, int nchunks,
                       unsigned long long* out_pairs, hipStream_t stream) {
+  if (chunk <= 0 || chunk > 16384 || (chunk & (chunk - 1)) != 0)  // the kernel's LDS array holds 16384
+    throw std::runtime_error("auc_count: chunk must be a power of two <= 16384");
   const int grid = stream_grid(n, kThreads * 8, 1024);
   auc_count_kernel<<<grid, kThreads, 0, stream>>>(scores, labels, n, pos, counter, chunk, nchunks,
                                                   out_pairs);
@@ -713,6 +715,7 @@ void launch_auc_hist(const float* scores, const uint8_t* labels, int64_t n, int 
 }
 
 void launch_auc_hist_reduce(const unsigned* hist, int bits, unsigned long long* out, hipStream_t stream) {
+  if (bits < 8 || bits > 24) throw std::runtime_error("auc_hist_reduce: bits must be in [8, 24]");
   auc_hist_reduce_kernel<<<1, 1024, 0, stream>>>(hist, bits, out);
   check_launch("auc_hist_reduce");
 }

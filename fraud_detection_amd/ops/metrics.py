@@ -86,8 +86,7 @@ def auc_pair_counts(scores: torch.Tensor, labels: torch.Tensor):
     if not scores.is_cuda:
         y = labels.numpy().astype(bool)
         P, N = int(y.sum()), int(n - y.sum())
-        auc = ref.roc_auc(scores.numpy(), y) if P and N else float("nan")
-        return (int(round(auc * 2 * P * N)) if P and N else 0), P, N
+        return ref.auc_twice_pairs(scores.numpy(), y), P, N  # the integer itself, not a rounded float
     if n >= RADIX_ROWS:
         _, res = auc_radix(scores, labels)
         twice, P, N = (int(v) for v in res.cpu())

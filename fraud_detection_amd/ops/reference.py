@@ -645,27 +645,43 @@ def smote_generate(C: np.ndarray, nbr: np.ndarray, q_offset: int, n_new: int, se
 # ------------------------------------------------------------------------------------------
 # K10 metrics
 # ------------------------------------------------------------------------------------------
+def _tie_groups(scores: np.ndarray):
+    """(order, starts, ends): the stable ascending order of the scores and the [start, end) bounds
+    of its tie groups.  Bounds come from ``!=`` on neighbours, not from a difference: inf - inf is
+    NaN, which would split a group of equal infinite scores into singletons."""
+    s = np.asarray(scores, dtype=np.float64).ravel()
+    order = np.argsort(s, kind="mergesort")
+    ss = s[order]
+    bounds = np.flatnonzero(ss[1:] != ss[:-1]) + 1
+    return order, np.concatenate([[0], bounds]), np.concatenate([bounds, [len(ss)]])
+
+
 def roc_auc(scores: np.ndarray, labels: np.ndarray) -> float:
-    """Exact ROC-AUC with averaged ties (== sklearn.metrics.roc_auc_score)."""
-    s = np.asarray(scores, dtype=np.float64)
-    y = np.asarray(labels).astype(bool)
+    """Exact ROC-AUC with averaged ties (== sklearn.metrics.roc_auc_score).  +-inf are ordinary
+    scores; NaN scores are not supported."""
+    y = np.asarray(labels).ravel().astype(bool)
     P, N = int(y.sum()), int((~y).sum())
     if P == 0 or N == 0:
         return float("nan")
-    order = np.argsort(s, kind="mergesort")
-    ss = s[order]
-    ranks = np.empty(len(s))
-    # average ranks over ties
-    i = 0
-    n = len(ss)
-    bounds = np.flatnonzero(np.diff(ss)) + 1
-    starts = np.concatenate([[0], bounds])
-    ends = np.concatenate([bounds, [n]])
-    avg = (starts + ends + 1) / 2.0
-    ranks_sorted = np.repeat(avg, ends - starts)
-    ranks[order] = ranks_sorted
-    del i
+    order, starts, ends = _tie_groups(scores)
+    ranks = np.empty(len(order))
+    avg = (starts + ends + 1) / 2.0  # average ranks over ties
+    ranks[order] = np.repeat(avg, ends - starts)
     return float((ranks[y].sum() - P * (P + 1) / 2.0) / (P * N))
+
+
+def auc_twice_pairs(scores: np.ndarray, labels: np.ndarray) -> int:
+    """2 #{s_p > s_n} + #{s_p == s_n} over (positive, negative) pairs as an exact Python integer
+    (roc_auc = this / (2 P N)): the sum over positives of twice their average rank,
+    start + end + 1 of their tie group, minus P (P + 1).  0 when a class is empty."""
+    y = np.asarray(labels).ravel().astype(bool)
+    P, N = int(y.sum()), int((~y).sum())
+    if P == 0 or N == 0:
+        return 0
+    order, starts, ends = _tie_groups(scores)
+    twice_rank = np.empty(len(order), dtype=np.int64)
+    twice_rank[order] = np.repeat((starts + ends + 1).astype(np.int64), ends - starts)
+    return int(twice_rank[y].sum(dtype=np.int64)) - P * (P + 1)  # each term <= 2 n + 1: exact below 2^31 rows
 
 
 def order_key(scores: np.ndarray) -> np.ndarray:
